@@ -11,9 +11,9 @@ Steps alternate over `--streams` (default 2) lanes per GPU: each lane is its own
 codec context + HIP stream + device-resident record (a partition's consecutive
 batches), and every step is one complete single-record decode through
 iggy_codec_decode_batch_device. Two lanes let one batch's serial batch-checksum
-tail overlap the next batch's streaming phase; the
-single-stream rate is reported beside it (`config.single_stream_gib_s`), and
-`roofline` prices one launch at a time.
+tail overlap the next batch's streaming phase; under
+`--full` the single-stream rate is reported beside it
+(`config.single_stream_gib_s`), and `roofline` prices one launch at a time.
 
 Multi-GPU (BASELINE configs[4], "C5"): one rank per GPU, each with its own
 independent partition's batch; no data-path collective (weak scaling). The
@@ -22,7 +22,12 @@ traffic. `--gpus N` without a launcher starts the N rank processes itself
 (before anything touches a GPU); under torch.distributed.run the ranks come
 from the environment.
 
-At N = 1 the line also carries, timed in the same run:
+A plain run does only what the headline figure needs: set up the lanes, warm up,
+time `--steps` steps, write the outputs (`--dump-outputs DIR`), print the line.
+Everything below is measured only under `--full`:
+  config.single_stream_gib_s  the same steps, one launch at a time on one stream;
+  roofline                    the decode grid's own duration (HIP events) against HBM peak;
+and at N = 1, timed in the same run (`--no-extra` / `--no-cpu` drop them again):
   c3_encode / c3_decode  BASELINE configs[2]: 1 M messages, payloads U[64, 4096] B,
                          device-resident encode (segmented lane-group path) and the
                          Verify decode of its output (general walk);
@@ -71,8 +76,13 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--messages", type=int, default=N_MSG)
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-extra", action="store_true", help="skip the c3 / c1 legs")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the single-stream rate, the roofline, the cpu_baseline and the "
+                         "c3 / c1 / c4 / encryption legs (a plain run times the headline steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the cpu_baseline leg")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the c3 / c1 legs")
     ap.add_argument("--cpu-seconds", type=float, default=4.0)
     ap.add_argument("--streams", type=int, default=2, help="decode lanes (contexts/streams) steps alternate over")
     ap.add_argument("--dry", action="store_true",
@@ -640,6 +650,30 @@ def pmc_traffic(n: int):
     return d.get("hbm_bytes_per_decode"), d.get("source")
 
 
+def dump_outputs(dirname: str, lane, world: int, rank: int):
+    """What a caller of the timed decode receives, as float64 .npy files: the frame
+    positions (every one below 2**53, so exact) and the fields of the result struct
+    (each u64 as its low and high 32-bit words, so the checksums stay exact). The
+    inputs are seeded, so two builds run with the same arguments compare file for file.
+    At N > 1 every rank writes its own partition's files, suffixed `_rank<r>`."""
+    suffix = f"_rank{rank}" if world > 1 else ""
+    os.makedirs(dirname, exist_ok=True)
+    pos = to_host(lane["pos"]).astype(np.float64)
+    cap = (60 << 20) // 8  # the files stay under 64 MB: a fixed seeded sample of a larger --messages
+    if pos.size > cap:
+        pos = pos[np.sort(np.random.default_rng(0).choice(pos.size, cap, replace=False))]
+    from iggy_amd import abi
+    res = abi.DecodeResult.from_buffer_copy(to_host(lane["res"]).tobytes())
+    h, e = res.header, res.error
+    words = []
+    for v in (h.partition_id, h.base_offset, h.base_timestamp, h.origin_timestamp, h.batch_length,
+              h.batch_checksum, h.message_count, e.kind, e.reason, e.a, e.b, e.c, res.frame_count,
+              res.computed_checksum, res.path, res.status, res.covered):
+        words += [v & 0xFFFFFFFF, v >> 32]
+    np.save(os.path.join(dirname, f"positions{suffix}.npy"), pos)
+    np.save(os.path.join(dirname, f"result{suffix}.npy"), np.array(words, dtype=np.float64))
+
+
 # --------------------------------------------------------------------- main
 def run(args, world: int, rank: int, local: int, dist):
     import torch
@@ -712,30 +746,51 @@ def run(args, world: int, rank: int, local: int, dist):
     # stream. `value` is the pipelined form, fixed up front (a partition's consecutive
     # batches in flight together; choosing the better of two single noisy timings after
     # the fact would bias the line upward); both numbers are in the line.
+    # A plain run times only the headline form; --full adds the single-stream form.
     elapsed_pipe = timed(step)
     check_lanes()
-    elapsed_single = timed(lambda i: step(0)) if len(lanes) > 1 else elapsed_pipe
-    check_lanes()
+    if args.dump_outputs:  # the lane the last timed step decoded into
+        dump_outputs(args.dump_outputs, lanes[(args.steps - 1) % len(lanes)], world, rank)
     elapsed = elapsed_pipe
     form = "pipelined" if len(lanes) > 1 else "single"
-
-    # roofline: the decode grid's own duration, one launch at a time on one
-    # stream (HIP events on the launch stream, bracketing k_decode_uniform)
-    cx = lanes[0]["cx"]
-    cx.profile_enable(True)
-    for _ in range(args.steps):
-        step(0)
-        torch.cuda.synchronize(dev)
-    launches, total_ms = cx.profile_read(0)
-    cx.profile_enable(False)
-    k_ms = total_ms / max(launches, 1)
-    alg_bytes = L + 8 * n  # read the record once + one 8-B frame position per message
-    achieved = alg_bytes / (k_ms * 1e-3) / 1e9
-    single_gib_s = L * args.steps / elapsed_single / 2**30
     pipe_gib_s = L * args.steps / elapsed_pipe / 2**30
+    single_gib_s = pipe_gib_s if len(lanes) == 1 else None
+    roofline = None
+    if args.full:
+        if len(lanes) > 1:
+            elapsed_single = timed(lambda i: step(0))
+            check_lanes()
+            single_gib_s = L * args.steps / elapsed_single / 2**30
+
+        # roofline: the decode grid's own duration, one launch at a time on one
+        # stream (HIP events on the launch stream, bracketing k_decode_uniform)
+        cx = lanes[0]["cx"]
+        cx.profile_enable(True)
+        for _ in range(args.steps):
+            step(0)
+            torch.cuda.synchronize(dev)
+        launches, total_ms = cx.profile_read(0)
+        cx.profile_enable(False)
+        k_ms = total_ms / max(launches, 1)
+        alg_bytes = L + 8 * n  # read the record once + one 8-B frame position per message
+        achieved = alg_bytes / (k_ms * 1e-3) / 1e9
+        traffic, traffic_src = pmc_traffic(n)
+        roofline = {
+            "bound": "hbm",
+            "achieved": round(achieved, 1),
+            "peak": HBM_PEAK_GBS,
+            "unit": "GB/s",
+            "frac": round(achieved / HBM_PEAK_GBS, 4),
+            "traffic": traffic,
+            "traffic_source": traffic_src,
+            "kernel": "k_decode_uniform<true> (one persistent grid: lane-group producers + chain WG), "
+                      "one launch at a time",
+            "kernel_ms": round(k_ms, 4),
+            "algorithmic_bytes": alg_bytes,
+        }
 
     extra = {}
-    if world == 1 and not args.no_extra:
+    if args.full and world == 1 and not args.no_extra:
         for ln in lanes[1:]:  # free HBM held by the other lanes' records
             ln["batch"] = None
         torch.cuda.empty_cache()
@@ -759,7 +814,7 @@ def run(args, world: int, rank: int, local: int, dist):
         torch.cuda.empty_cache()
         extra["c4"] = leg("c4", lambda: c4_leg(dev, 16))
     cpu = None
-    if rank == 0 and not args.no_cpu:
+    if args.full and rank == 0 and not args.no_cpu:
         # N = 1: the full sample; N > 1: a short one (1 thread and one per rank) so the
         # scaling lines carry the CPU axis too without lengthening the run much
         try:
@@ -768,7 +823,6 @@ def run(args, world: int, rank: int, local: int, dist):
         except Exception as ex:  # reported in the line, never silently dropped
             cpu = {"error": f"{type(ex).__name__}: {ex}"[:500]}
 
-    traffic, traffic_src = pmc_traffic(n)
     value = whole_job_gib_s(world, L, args.steps, elapsed)
     line = {
         "metric": METRIC,
@@ -793,24 +847,13 @@ def run(args, world: int, rank: int, local: int, dist):
             "parallelism": f"{world} independent partitions, one per GPU, no collective",
             "streams_per_gpu": len(lanes),
             "value_form": form,
-            "single_stream_gib_s": round(single_gib_s, 2),
+            "single_stream_gib_s": round(single_gib_s, 2) if single_gib_s is not None else None,
             "pipelined_gib_s": round(pipe_gib_s, 2),
             "per_gpu_gib_s": round(value / world, 2),
             "per_gpu_hbm_frac": round(value / world * 2**30 / 1e9 / HBM_PEAK_GBS, 4),
         },
-        "roofline": {
-            "bound": "hbm",
-            "achieved": round(achieved, 1),
-            "peak": HBM_PEAK_GBS,
-            "unit": "GB/s",
-            "frac": round(achieved / HBM_PEAK_GBS, 4),
-            "traffic": traffic,
-            "traffic_source": traffic_src,
-            "kernel": "k_decode_uniform<true> (one persistent grid: lane-group producers + chain WG), "
-                      "one launch at a time",
-            "kernel_ms": round(k_ms, 4),
-            "algorithmic_bytes": alg_bytes,
-        },
+        "full": bool(args.full),
+        "roofline": roofline,
         "cpu_baseline": cpu,
     }
     line.update(extra)

@@ -13,7 +13,7 @@ for s in $STEPS; do
   case $s in
     tests) timeout -k 10 600 python -u -m pytest ${TESTS:-tests} -m gpu -x -v --timeout 200 --timeout-method thread > $O/tests.log 2>&1 ;;
     smoke) timeout -k 10 200 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1 ;;
-    bench) timeout -k 10 400 python -u bench.py ${BENCH_ARGS:-} > $O/bench.log 2>&1 ;;
+    bench) timeout -k 10 400 python -u bench.py --full ${BENCH_ARGS:-} > $O/bench.log 2>&1 ;;
     phase) timeout -k 10 200 python -u scripts/diag_general.py ${DG_ARGS:-} > $O/phase.log 2>&1 ;;
     records) timeout -k 10 300 python -u scripts/records_bench.py > $O/records.log 2>&1 ;;
     *) echo "unknown step $s"; exit 2 ;;

@@ -8,7 +8,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/prof_${1:-r}
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-B="$R/bench.py --streams 1 --no-cpu --no-extra"
+B="$R/bench.py --full --streams 1 --no-cpu --no-extra"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/iso -o iso -- python3 $B --steps 20 --warmup 3 > $O/iso.log 2>&1
 rc=$?; echo "iso rc=$rc" >> $O/iso.log; [ $rc -eq 0 ] || exit $rc
 timeout -s KILL 150 rocprofv3 --pmc FETCH_SIZE --output-format rocpd csv -d $O/pmc1 -o pmc -- python3 $B --steps 5 --warmup 2 > $O/pmc1.log 2>&1

@@ -344,6 +344,53 @@ class ProducerRequest(ctypes.Structure):
                 ("entry", u32), ("sent", u32), ("error", WireError)]
 
 
+class UnpackedMessages(ctypes.Structure):
+    """iggy_unpacked_messages: device output arrays of the consumer unpack (None = not wanted)."""
+    _fields_ = [
+        ("cap_messages", u64),
+        ("cap_payload_bytes", u64),
+        ("cap_user_headers_bytes", u64),
+        ("ids", ctypes.c_void_p),
+        ("checksums", ctypes.c_void_p),
+        ("offsets", ctypes.c_void_p),
+        ("timestamps", ctypes.c_void_p),
+        ("origin_timestamps", ctypes.c_void_p),
+        ("payload_lengths", ctypes.c_void_p),
+        ("user_headers_lengths", ctypes.c_void_p),
+        ("payload_starts", ctypes.c_void_p),
+        ("user_headers_starts", ctypes.c_void_p),
+        ("payloads", ctypes.c_void_p),
+        ("user_headers", ctypes.c_void_p),
+    ]
+
+
+class UnpackCursor(ctypes.Structure):
+    """iggy_unpack_cursor: running totals of chained unpacks (device memory)."""
+    _fields_ = [("messages", u64), ("payload_bytes", u64), ("user_headers_bytes", u64), ("_pad", u64)]
+
+    def astuple(self):
+        return (self.messages, self.payload_bytes, self.user_headers_bytes)
+
+
+class UnpackResult(ctypes.Structure):
+    """iggy_unpack_result: the device-resident outcome of one unpack."""
+    _fields_ = [
+        ("error", WireError),
+        ("count", u64),
+        ("payload_bytes", u64),
+        ("user_headers_bytes", u64),
+        ("first_message", u64),
+        ("min_payload_length", u32),
+        ("max_payload_length", u32),
+        ("_pad", u64),
+    ]
+
+
+assert ctypes.sizeof(UnpackedMessages) == 112
+assert ctypes.sizeof(UnpackCursor) == 32
+assert ctypes.sizeof(UnpackResult) == 80
+
+
 class PollFragment(ctypes.Structure):
     """iggy_poll_fragment: one host span of a poll reply (PollFragments)."""
     _fields_ = [("data", ctypes.c_void_p), ("len", u64)]

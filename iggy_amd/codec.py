@@ -111,6 +111,7 @@ def load(path: str) -> ctypes.CDLL:
     L.iggy_codec_select_slice.argtypes = [vp, vp, u64, vp, vp, vp, vp]
     L.iggy_codec_select_slice_device.argtypes = [vp, vp, vp, u64, vp, vp, vp, vp]
     L.iggy_codec_stamp_batch_device.argtypes = [vp, vp, vp, u64, u64, u64, vp, vp]
+    L.iggy_codec_unpack_batch_device.argtypes = [vp, vp, u64, vp, vp, vp, vp, vp, vp]
     L.iggy_codec_decode_prepare.argtypes = [vp, vp, u64, ci, vp, vp]
     L.iggy_codec_admit_batch.argtypes = [vp, vp, u64, u32, u64, ci, vp, u64, vp, vp]
     L.iggy_codec_recover_segment.argtypes = [vp, vp, u64, u64, vp]
@@ -469,6 +470,14 @@ class Codec:
                      d_header: int | None = None, stream: int | None = None) -> int:
         return self._L.iggy_codec_stamp_batch_device(self._h, d_record, d_frame_pos, nframes, base_offset,
                                                      base_timestamp, d_header, stream)
+
+    def unpack_device(self, d_record: int, length: int, d_frame_pos: int | None, d_decode: int,
+                      out: abi.UnpackedMessages, d_cursor: int | None, d_result: int,
+                      stream: int | None = None) -> int:
+        """iggy_codec_unpack_batch_device: a decoded device record into the SoA arrays of `out`
+        (device pointers). Result: abi.UnpackResult at d_result."""
+        return self._L.iggy_codec_unpack_batch_device(self._h, d_record, length, d_frame_pos, d_decode,
+                                                      ctypes.byref(out), d_cursor, d_result, stream)
 
     # --------------------------------------------------------- device buffers
     def decode_device(self, d_body: int, length: int, integrity: int, d_frame_pos: int | None,

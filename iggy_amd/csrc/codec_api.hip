@@ -36,6 +36,7 @@
 #include "poll.hip"
 #include "slice.hip"
 #include "crypt.hip"
+#include "unpack.hip"
 static_assert(!IGGY_ENC_SPLIT || iggy::kErWaves == 4, "the writer-wave split is built for 4 hasher waves");
 
 using namespace iggy;
@@ -62,6 +63,7 @@ using namespace iggy;
 //   host_crypt    at-rest encryption host setup
 //   host_pollbody poll reply body
 //   host_slice    poll-path slicing, disk-chunk walk, device stamp
+//   host_unpack   consumer unpack (struct-of-arrays output)
 //   host_async    asynchronous submit / poll / wait
 #include "host_ctx.hpp"
 #include "host_mem.hpp"
@@ -72,6 +74,7 @@ using namespace iggy;
 #include "host_crypt.hpp"
 #include "host_pollbody.hpp"
 #include "host_slice.hpp"
+#include "host_unpack.hpp"
 #include "host_async.hpp"
 
 
@@ -207,7 +210,7 @@ void iggy_codec_destroy(iggy_codec_ctx *c) {
                       &c->gbsums, &c->dresult, &c->din, &c->dpos, &c->dout, &c->epl, &c->euh,
                       &c->etile, &c->ecs, &c->emisc, &c->eids, &c->eots, &c->epay, &c->eplen,
                       &c->euhb, &c->euhl, &c->erec, &c->esink, &c->hbsums, &c->ppos, &c->pmsgs, &c->pres, &c->cwk, &c->sl, &c->slres, &c->cr,
-                      &c->rtab, &c->rbsums, &c->rres, &c->clinks, &c->rstate, &c->rcount, &c->pbres};
+                      &c->rtab, &c->rbsums, &c->rres, &c->clinks, &c->rstate, &c->rcount, &c->pbres, &c->up};
     for (DevBuf *b : bufs) b->release();
     if (c->h_pinned) (void)hipHostFree(c->h_pinned);
     if (c->pb_pinned) (void)hipHostFree(c->pb_pinned);
@@ -258,7 +261,8 @@ int iggy_codec_reserve(iggy_codec_ctx *c, uint64_t max_batch_bytes, uint64_t max
     DevGuard dg(c->device);
     bind(c, nullptr);
     (void)max_frames;
-    return ensure_decode_scratch(c, max_batch_bytes);
+    if (int r = ensure_decode_scratch(c, max_batch_bytes)) return r;
+    return ensure_unpack_scratch(c, max_batch_bytes);
 }
 
 void *iggy_codec_stream(iggy_codec_ctx *c) { return c ? (void *)c->stream : nullptr; }

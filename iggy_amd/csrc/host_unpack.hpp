@@ -1,0 +1,75 @@
+// host_unpack.hpp -- consumer unpack: scratch sizing and the enqueue of unpack.hip
+//
+// Part of the unity build of libiggy_codec.so: included by codec_api.hip, after the
+// kernel translation units and the units before it (see codec_api.hip for the order).
+#pragma once
+
+namespace {
+
+// frames a record of `len` bytes can hold (48-B headers tiling its blob)
+inline uint64_t unpack_max_frames(uint64_t len) { return len > kHdr ? (len - kHdr) / kFrameHdr + 1 : 1; }
+
+// [0, 256) control words | tile sums (payload, user headers) | tile min / max | per-frame lengths
+int ensure_unpack_scratch(iggy_codec_ctx *c, uint64_t len) {
+    const uint64_t frames = unpack_max_frames(len);
+    if (frames <= c->up_frames && c->up.p) return 0;
+    const uint64_t ntiles = frames / kUpTile + 2;
+    if (c->up.ensure(256 + ntiles * 24 + frames * 8)) return IGGY_ERR_DEVICE;
+    c->up_frames = frames;
+    return 0;
+}
+
+UnpackScratch uscratch(iggy_codec_ctx *c) {
+    const uint64_t ntiles = c->up_frames / kUpTile + 2;
+    UnpackScratch us;
+    us.ctl = c->up.as<uint64_t>(0);
+    us.tile_pl = c->up.as<uint64_t>(256);
+    us.tile_uh = c->up.as<uint64_t>(256 + ntiles * 8);
+    us.tile_mm = c->up.as<uint32_t>(256 + ntiles * 16);
+    us.lens = c->up.as<uint2>(256 + ntiles * 24);
+    us.max_frames = c->up_frames;
+    return us;
+}
+
+}  // namespace
+
+extern "C" {
+
+int iggy_codec_unpack_batch_device(iggy_codec_ctx *c, const uint8_t *d_record, uint64_t len,
+                                   const uint64_t *d_frame_pos, const iggy_decode_result *d_decode,
+                                   const iggy_unpacked_messages *out, iggy_unpack_cursor *d_cursor,
+                                   iggy_unpack_result *d_result, void *stream) {
+    if (!c || !d_record || !d_decode || !out || !d_result || len < kHdr) return IGGY_ERR_INVALID_ARGUMENT;
+    if ((out->payloads && !out->payload_starts) || (out->user_headers && !out->user_headers_starts))
+        return IGGY_ERR_INVALID_ARGUMENT;
+    const uint64_t max_frames = unpack_max_frames(len);
+    if (!d_frame_pos && len > kHdr) return IGGY_ERR_INVALID_ARGUMENT;
+    DevGuard dg(c->device);
+    hipStream_t s = bind(c, stream);
+    // (sized by iggy_codec_reserve; grown here only for a record larger than any before)
+    if (int r = ensure_unpack_scratch(c, len)) return r;
+    const UnpackScratch us = uscratch(c);
+    // grids from the record's length and the capacities alone: the count stays on the device
+    const uint64_t wgs = (uint64_t)c->ncu * 8;
+    const uint32_t gtiles = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((max_frames + kUpTile - 1) / kUpTile, wgs));
+    hipLaunchKernelGGL(k_unpack_fields, dim3(gtiles), dim3(256), 0, s, d_record, len, d_frame_pos, d_decode, *out,
+                       (const iggy_unpack_cursor *)d_cursor, us);
+    hipLaunchKernelGGL(k_unpack_scan, dim3(1), dim3(256), 0, s, len, d_decode, *out, d_cursor, us, d_result);
+    if (out->payload_starts || out->user_headers_starts)
+        hipLaunchKernelGGL(k_unpack_starts, dim3(gtiles), dim3(256), 0, s, *out, us);
+    const uint64_t blob = len - kHdr;
+    if (out->payloads && blob) {
+        const uint64_t spans = std::min(out->cap_payload_bytes, blob) / kUpSpan + 2;
+        hipLaunchKernelGGL(k_unpack_copy, dim3((uint32_t)std::min(spans, wgs)), dim3(256), 0, s, d_record, d_frame_pos,
+                           (const uint64_t *)out->payload_starts, out->payloads, 0u, us);
+    }
+    if (out->user_headers && blob) {
+        const uint64_t spans = std::min(out->cap_user_headers_bytes, blob) / kUpSpan + 2;
+        hipLaunchKernelGGL(k_unpack_copy, dim3((uint32_t)std::min(spans, wgs)), dim3(256), 0, s, d_record, d_frame_pos,
+                           (const uint64_t *)out->user_headers_starts, out->user_headers, 1u, us);
+    }
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+}  // extern "C"

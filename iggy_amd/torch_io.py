@@ -33,6 +33,88 @@ def to_device(a, device="cuda"):
     return p.to(device)
 
 
+def unpack_record(cx, d_record, integrity: int = 0, cursor=None) -> dict:
+    """Decode the device-resident record `d_record` (a uint8 CUDA tensor) and unpack it
+    into struct-of-arrays torch tensors (iggy_codec_unpack_batch_device): decode and
+    unpack are enqueued back to back on the current stream, then ONE synchronise.
+
+    Returns a dict of tensors trimmed to the record's `count` messages: ids [count, 2],
+    checksums, offsets, timestamps, origin_timestamps, payload_lengths,
+    user_headers_lengths, payload_starts / user_headers_starts [count + 1], payloads,
+    user_headers, plus `count`, `first_message` and, when every payload has one length L,
+    `payloads_2d`, a [count, L] view of `payloads`. Raises CodecError carrying the wire
+    error when the record does not decode (or an enqueue fails).
+
+    cursor: an optional int64 CUDA tensor of 4 (an iggy_unpack_cursor) that this call
+    advances; its totals are read first (one small copy) so that the arrays hold
+    them, and the returned tensors are this record's part (the starts stay absolute)."""
+    import ctypes
+
+    import torch
+
+    from . import abi
+    from .codec import CodecError
+
+    if d_record.dtype != torch.uint8 or not d_record.is_cuda or not d_record.is_contiguous():
+        raise ValueError("d_record must be a contiguous uint8 CUDA tensor")
+    n = d_record.numel()
+    dev = d_record.device
+    bm = bp = bu = 0
+    if cursor is not None:
+        bm, bp, bu = (int(x) for x in to_host(cursor)[:3])
+    cap_m = n // 48 + 1
+    cap_b = max(n - 256, 0)
+
+    def arr(k, dtype):
+        return torch.empty(max(k, 1), dtype=dtype, device=dev)
+
+    i64 = torch.int64  # (torch has no uint64 arithmetic: the u64 arrays are int64 bit patterns)
+    t = {
+        "ids": arr(2 * (bm + cap_m), i64), "checksums": arr(bm + cap_m, i64), "offsets": arr(bm + cap_m, i64),
+        "timestamps": arr(bm + cap_m, i64), "origin_timestamps": arr(bm + cap_m, i64),
+        "payload_lengths": arr(bm + cap_m, torch.int32), "user_headers_lengths": arr(bm + cap_m, torch.int32),
+        "payload_starts": arr(bm + cap_m + 1, i64), "user_headers_starts": arr(bm + cap_m + 1, i64),
+        "payloads": arr(bp + cap_b, torch.uint8), "user_headers": arr(bu + cap_b, torch.uint8),
+    }
+    out = abi.UnpackedMessages(bm + cap_m, bp + cap_b, bu + cap_b, *(t[k].data_ptr() for k in (
+        "ids", "checksums", "offsets", "timestamps", "origin_timestamps", "payload_lengths",
+        "user_headers_lengths", "payload_starts", "user_headers_starts", "payloads", "user_headers")))
+    d_pos = arr(cap_m, i64)
+    d_dec = torch.zeros(ctypes.sizeof(abi.DecodeResult), dtype=torch.uint8, device=dev)
+    d_res = torch.zeros(ctypes.sizeof(abi.UnpackResult), dtype=torch.uint8, device=dev)
+    # torch's default stream is handle 0, which the C ABI reads as "the context's own
+    # stream": then the work goes there, ordered after and before torch's stream by events
+    cur = torch.cuda.current_stream(dev)
+    work = cur if cur.cuda_stream else torch.cuda.ExternalStream(cx.stream(), device=dev)
+    if work is not cur:
+        work.wait_stream(cur)
+    s = work.cuda_stream
+    rc = cx.decode_device(d_record.data_ptr(), n, integrity, d_pos.data_ptr(), cap_m, d_dec.data_ptr(), s)
+    if rc:
+        raise CodecError(rc, None, "unpack_record: decode")
+    rc = cx.unpack_device(d_record.data_ptr(), n, d_pos.data_ptr(), d_dec.data_ptr(), out,
+                          cursor.data_ptr() if cursor is not None else None, d_res.data_ptr(), s)
+    if rc:
+        raise CodecError(rc, None, "unpack_record: unpack")
+    if work is not cur:
+        cur.wait_stream(work)
+    res =abi.UnpackResult.from_buffer_copy(to_host(d_res).tobytes())  # the one synchronise
+    if res.error.kind != abi.OK:
+        raise CodecError(res.error.kind, res.error, "unpack_record")
+    c, f = res.count, res.first_message
+    r = {k: t[k][f:f + c] for k in ("checksums", "offsets", "timestamps", "origin_timestamps",
+                                    "payload_lengths", "user_headers_lengths")}
+    r["ids"] = t["ids"][2 * f:2 * (f + c)].view(c, 2)
+    r["payload_starts"] = t["payload_starts"][f:f + c + 1]
+    r["user_headers_starts"] = t["user_headers_starts"][f:f + c + 1]
+    r["payloads"] = t["payloads"][bp:bp + res.payload_bytes]
+    r["user_headers"] = t["user_headers"][bu:bu + res.user_headers_bytes]
+    r["count"], r["first_message"] = c, f
+    if c and res.min_payload_length == res.max_payload_length:
+        r["payloads_2d"] = r["payloads"].view(c, res.max_payload_length)
+    return r
+
+
 def to_host(t) -> np.ndarray:
     """A numpy copy of tensor `t` (synchronous; the copy lands in pinned memory)."""
     import torch

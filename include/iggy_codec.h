@@ -447,6 +447,78 @@ int iggy_codec_stamp_batch_device(iggy_codec_ctx *ctx, uint8_t *d_record, const 
                                   uint64_t nframes, uint64_t base_offset, uint64_t base_timestamp,
                                   iggy_batch_header *d_header, void *stream);
 
+/* ------------------------------------------------------------ consumer unpack */
+/* A verified device-resident record back into arrays: the device form of the SDK's
+ * consumer decode (PolledMessages::messages_from_batches, common/src/types/message/
+ * polled_messages.rs:95-150, over PolledBatchesIterator, binary_protocol/src/responses/
+ * messages/poll_messages.rs:132-165) with the struct-of-arrays shape of the encoder's
+ * input (RawMessage, requests/messages/send_messages.rs:37-42), so that its output is
+ * an iggy_raw_messages for iggy_codec_encode_batch_device (unpack -> encode re-batches
+ * on the device).
+ *
+ * Output arrays, all DEVICE pointers; any array pointer may be NULL (= not wanted).
+ * Shapes mirror iggy_raw_messages so the result feeds iggy_codec_encode_batch_device. */
+typedef struct iggy_unpacked_messages {
+    uint64_t cap_messages;          /* capacity of every per-message array, in messages      */
+    uint64_t cap_payload_bytes;     /* capacity of payloads                                  */
+    uint64_t cap_user_headers_bytes;/* capacity of user_headers                              */
+    uint64_t *ids;                  /* 2 per message: id_lo, id_hi                           */
+    uint64_t *checksums;            /* stored per-message checksum                           */
+    uint64_t *offsets;              /* base_offset + offset_delta, wrapping (k_poll_fill)    */
+    uint64_t *timestamps;           /* base_timestamp, flat per batch                        */
+    uint64_t *origin_timestamps;    /* origin_timestamp + timestamp_delta                    */
+    uint32_t *payload_lengths;
+    uint32_t *user_headers_lengths;
+    uint64_t *payload_starts;       /* cap_messages + 1 entries: byte start in payloads,     */
+    uint64_t *user_headers_starts;  /*   entry [count] = end (exclusive prefix sums)         */
+    uint8_t  *payloads;             /* every payload, message order, no gaps                 */
+    uint8_t  *user_headers;
+} iggy_unpacked_messages;
+
+/* Running totals for chaining several records into one set of arrays without a
+ * host round trip (a poll body's records, one after the other). Device memory. */
+typedef struct iggy_unpack_cursor { uint64_t messages, payload_bytes, user_headers_bytes, _pad; } iggy_unpack_cursor;
+
+typedef struct iggy_unpack_result {
+    iggy_wire_error error;          /* OK, the decode's own error, or IGGY_ERR_CAPACITY      */
+    uint64_t count;                 /* messages of THIS record (0 on any error)              */
+    uint64_t payload_bytes, user_headers_bytes;           /* of this record                  */
+    uint64_t first_message;         /* index of this record's message 0 in the arrays        */
+    uint32_t min_payload_length, max_payload_length;      /* equal => payloads is [count][L] */
+    uint64_t _pad;
+} iggy_unpack_result;
+
+/* Unpacks the record at d_record (len >= 256 bytes) that iggy_codec_decode_batch_device
+ * decoded (either integrity) into d_frame_pos / *d_decode. Everything is enqueued on
+ * `stream` (no synchronisation): the kernels read the message count from
+ * d_decode->frame_count on the device, so a decode and its unpack queue back to back
+ * with no host wait; the launches (at most five, whatever the count) are sized from len
+ * and the capacities. *out is a host struct of device pointers.
+ *  - d_decode->error.kind != IGGY_OK, or a status other than done: d_result->error is
+ *    that error (IGGY_ERR_INVALID_ARGUMENT for a result that is not final or does not
+ *    fit a record of len bytes), count = 0, no output array is written, the cursor stays.
+ *  - with d_cursor (nullable; bases 0 without) this record's messages land at message
+ *    index cursor.messages, its payloads at byte cursor.payload_bytes of `payloads`, its
+ *    user headers likewise; payload_starts[first_message + i] are absolute positions in
+ *    `payloads`, and entry [first_message + count] of each starts array is written too
+ *    (chained records share it). The cursor advances on success only.
+ *  - capacity is checked on the device before any payload byte is copied: first_message
+ *    + count > cap_messages, or the payload (user-header) total with the cursor's base
+ *    above cap_payload_bytes (cap_user_headers_bytes) when that array is wanted, gives
+ *    IGGY_ERR_CAPACITY with a = messages, b = payload bytes, c = user-header bytes the
+ *    arrays would need (bases included); array contents inside the capacities are then
+ *    unspecified, nothing beyond a capacity is ever written, the cursor stays.
+ *  - offsets are base_offset + offset_delta with wrapping addition; sums and starts are
+ *    u64 (the server encoder has no u32 cap, server_common/src/send_messages.rs:104-168).
+ * Returns IGGY_ERR_INVALID_ARGUMENT synchronously for a null ctx, record, decode, out or
+ * result, len < 256, no d_frame_pos for a record with a body, or a wanted payloads /
+ * user_headers without its starts array. Scratch is the context's (iggy_codec_reserve
+ * sizes it; a record larger than any before grows it outside the stream order). */
+int iggy_codec_unpack_batch_device(iggy_codec_ctx *ctx, const uint8_t *d_record, uint64_t len,
+                                   const uint64_t *d_frame_pos, const iggy_decode_result *d_decode,
+                                   const iggy_unpacked_messages *out, iggy_unpack_cursor *d_cursor /* nullable */,
+                                   iggy_unpack_result *d_result, void *stream);
+
 /* ------------------------------------------------- server admission / prepare */
 /* PrepareHeader.size (u32) sits at byte 48 of the 256-B consensus header
  * (binary_protocol/src/consensus/header.rs:901-932); the batch header follows it. */

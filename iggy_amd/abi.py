@@ -391,6 +391,68 @@ assert ctypes.sizeof(UnpackCursor) == 32
 assert ctypes.sizeof(UnpackResult) == 80
 
 
+# ---- user headers (include/iggy_codec.h "user headers")
+ERR_INVALID_HEADER_KEY = 27
+ERR_INVALID_HEADER_VALUE = 28
+ERR_INVALID_HEADER_KIND = 29
+V_HEADER_KIND_ZERO = 11
+V_HEADER_FIELD_LENGTH = 12
+V_HEADER_ODD_ENTRIES = 13
+HEADER_MAX_KEYS = 16
+HEADER_MAX_KEY_BYTES = 1024
+# HeaderKind codes (common/src/types/message/user_headers.rs:231-247)
+(KIND_RAW, KIND_STRING, KIND_BOOL, KIND_INT8, KIND_INT16, KIND_INT32, KIND_INT64, KIND_INT128, KIND_UINT8,
+ KIND_UINT16, KIND_UINT32, KIND_UINT64, KIND_UINT128, KIND_FLOAT32, KIND_FLOAT64) = range(1, 16)
+
+
+class HeaderKey(ctypes.Structure):
+    """iggy_header_key: one requested key, (kind code, key bytes)."""
+    _fields_ = [("kind", ctypes.c_uint8), ("length", ctypes.c_uint8), ("bytes", ctypes.c_uint8 * 255),
+                ("_pad", ctypes.c_uint8 * 7)]
+
+    @classmethod
+    def make(cls, kind: int, key: bytes) -> "HeaderKey":
+        """(no check here: the entry points refuse a malformed key)"""
+        x = cls()
+        key = bytes(key)[:255]
+        x.kind, x.length = kind, len(key)
+        ctypes.memmove(x.bytes, key, len(key))
+        return x
+
+
+class HeaderStatus(ctypes.Structure):
+    """iggy_header_status: one message's verdict."""
+    _fields_ = [("kind", u32), ("reason", u32), ("offset", u32), ("detail", u32)]
+
+    def astuple(self):
+        return (self.kind, self.reason, self.offset, self.detail)
+
+
+class HeaderColumn(ctypes.Structure):
+    """iggy_header_column: one key's device columns (None = not wanted)."""
+    _fields_ = [("value_kinds", ctypes.c_void_p), ("value_lengths", ctypes.c_void_p),
+                ("value_pos", ctypes.c_void_p), ("values16", ctypes.c_void_p)]
+
+
+class HeaderColumns(ctypes.Structure):
+    """iggy_header_columns: the request (host struct of keys and device pointers)."""
+    _fields_ = [("cap_messages", u64), ("nkeys", u32), ("_pad", u32), ("keys", HeaderKey * 16),
+                ("columns", HeaderColumn * 16), ("status", ctypes.c_void_p), ("pairs", ctypes.c_void_p)]
+
+
+class HeaderColumnsResult(ctypes.Structure):
+    """iggy_header_columns_result: the device-resident outcome of one call."""
+    _fields_ = [("error", WireError), ("count", u64), ("with_headers", u64), ("invalid_messages", u64),
+                ("first_invalid", u64), ("found", u64 * 16)]
+
+
+assert ctypes.sizeof(HeaderKey) == 264
+assert ctypes.sizeof(HeaderStatus) == 16
+assert ctypes.sizeof(HeaderColumn) == 32
+assert ctypes.sizeof(HeaderColumns) == 16 + 16 * 264 + 16 * 32 + 16
+assert ctypes.sizeof(HeaderColumnsResult) == 192
+
+
 class PollFragment(ctypes.Structure):
     """iggy_poll_fragment: one host span of a poll reply (PollFragments)."""
     _fields_ = [("data", ctypes.c_void_p), ("len", u64)]

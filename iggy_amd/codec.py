@@ -112,6 +112,10 @@ def load(path: str) -> ctypes.CDLL:
     L.iggy_codec_select_slice_device.argtypes = [vp, vp, vp, u64, vp, vp, vp, vp]
     L.iggy_codec_stamp_batch_device.argtypes = [vp, vp, vp, u64, u64, u64, vp, vp]
     L.iggy_codec_unpack_batch_device.argtypes = [vp, vp, u64, vp, vp, vp, vp, vp, vp]
+    L.iggy_codec_user_headers_device.argtypes = [vp, vp, u64, vp, vp, vp, vp, vp]
+    L.iggy_codec_user_headers_arrays_device.argtypes = [vp, vp, vp, vp, u64, vp, vp, vp]
+    L.iggy_user_headers_validate.argtypes = [vp, u64, vp, vp]
+    L.iggy_user_headers_get.argtypes = [vp, u64, vp, vp, vp, vp, vp]
     L.iggy_codec_decode_prepare.argtypes = [vp, vp, u64, ci, vp, vp]
     L.iggy_codec_admit_batch.argtypes = [vp, vp, u64, u32, u64, ci, vp, u64, vp, vp]
     L.iggy_codec_recover_segment.argtypes = [vp, vp, u64, u64, vp]
@@ -478,6 +482,24 @@ class Codec:
         (device pointers). Result: abi.UnpackResult at d_result."""
         return self._L.iggy_codec_unpack_batch_device(self._h, d_record, length, d_frame_pos, d_decode,
                                                       ctypes.byref(out), d_cursor, d_result, stream)
+
+    def user_headers_device(self, d_record: int, length: int, d_frame_pos: int | None, d_decode: int,
+                            q: abi.HeaderColumns, d_result: int, stream: int | None = None) -> int:
+        """iggy_codec_user_headers_device: the user headers of a decoded device record validated
+        and the keys of `q` projected into its columns (device pointers). Enqueue only; the
+        result is an abi.HeaderColumnsResult at d_result."""
+        return self._L.iggy_codec_user_headers_device(self._h, d_record, length, d_frame_pos, d_decode,
+                                                      ctypes.byref(q), d_result, stream)
+
+    def user_headers_arrays_device(self, d_user_headers: int | None, d_user_headers_starts: int, d_count: int,
+                                   cap_messages_hint: int, q: abi.HeaderColumns, d_result: int,
+                                   stream: int | None = None) -> int:
+        """iggy_codec_user_headers_arrays_device: the same over the user_headers /
+        user_headers_starts arrays an unpack wrote; *d_count (device, e.g. the cursor's
+        `messages`) is the message count."""
+        return self._L.iggy_codec_user_headers_arrays_device(self._h, d_user_headers, d_user_headers_starts,
+                                                             d_count, cap_messages_hint, ctypes.byref(q),
+                                                             d_result, stream)
 
     # --------------------------------------------------------- device buffers
     def decode_device(self, d_body: int, length: int, integrity: int, d_frame_pos: int | None,

@@ -37,6 +37,7 @@
 #include "slice.hip"
 #include "crypt.hip"
 #include "unpack.hip"
+#include "user_headers.hip"
 static_assert(!IGGY_ENC_SPLIT || iggy::kErWaves == 4, "the writer-wave split is built for 4 hasher waves");
 
 using namespace iggy;
@@ -64,6 +65,7 @@ using namespace iggy;
 //   host_pollbody poll reply body
 //   host_slice    poll-path slicing, disk-chunk walk, device stamp
 //   host_unpack   consumer unpack (struct-of-arrays output)
+//   host_user_headers  user-header validation and key columns
 //   host_async    asynchronous submit / poll / wait
 #include "host_ctx.hpp"
 #include "host_mem.hpp"
@@ -75,6 +77,7 @@ using namespace iggy;
 #include "host_pollbody.hpp"
 #include "host_slice.hpp"
 #include "host_unpack.hpp"
+#include "host_user_headers.hpp"
 #include "host_async.hpp"
 
 
@@ -210,7 +213,7 @@ void iggy_codec_destroy(iggy_codec_ctx *c) {
                       &c->gbsums, &c->dresult, &c->din, &c->dpos, &c->dout, &c->epl, &c->euh,
                       &c->etile, &c->ecs, &c->emisc, &c->eids, &c->eots, &c->epay, &c->eplen,
                       &c->euhb, &c->euhl, &c->erec, &c->esink, &c->hbsums, &c->ppos, &c->pmsgs, &c->pres, &c->cwk, &c->sl, &c->slres, &c->cr,
-                      &c->rtab, &c->rbsums, &c->rres, &c->clinks, &c->rstate, &c->rcount, &c->pbres, &c->up};
+                      &c->rtab, &c->rbsums, &c->rres, &c->clinks, &c->rstate, &c->rcount, &c->pbres, &c->up, &c->uh};
     for (DevBuf *b : bufs) b->release();
     if (c->h_pinned) (void)hipHostFree(c->h_pinned);
     if (c->pb_pinned) (void)hipHostFree(c->pb_pinned);
@@ -373,6 +376,9 @@ const char *iggy_codec_error_string(uint32_t kind, uint32_t reason) {
                 case IGGY_V_BALANCED_LENGTH: return "balanced partitioning must have length 0";
                 case IGGY_V_PARTITION_ID_LENGTH: return "partition_id partitioning must have length 4";
                 case IGGY_V_MESSAGES_KEY_EMPTY: return "messages_key partitioning cannot have empty key";
+                case IGGY_V_HEADER_KIND_ZERO: return "header kind is 0 (reserved)";
+                case IGGY_V_HEADER_FIELD_LENGTH: return "header field length out of range 1..=255";
+                case IGGY_V_HEADER_ODD_ENTRIES: return "odd number of TLV entries, expected key-value pairs";
                 default: return "validation failed";
             }
         case IGGY_ERR_INVALID_BATCH_CHECKSUM: return "invalid batch checksum";
@@ -383,6 +389,9 @@ const char *iggy_codec_error_string(uint32_t kind, uint32_t reason) {
         case IGGY_ERR_UNKNOWN_DISCRIMINANT: return "unknown discriminant";
         case IGGY_ERR_INVALID_NUMBER_ENCODING: return "invalid number encoding";
         case IGGY_ERR_INVALID_MESSAGE_PAYLOAD_LENGTH: return "invalid message payload length";
+        case IGGY_ERR_INVALID_HEADER_KEY: return "invalid header key";
+        case IGGY_ERR_INVALID_HEADER_VALUE: return "invalid header value";
+        case IGGY_ERR_INVALID_HEADER_KIND: return "invalid header kind";
         case IGGY_ERR_DEVICE: return "device error";
         case IGGY_ERR_INVALID_ARGUMENT: return "invalid argument";
         case IGGY_ERR_CAPACITY: return "output capacity too small";

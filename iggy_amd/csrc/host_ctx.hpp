@@ -234,6 +234,7 @@ struct iggy_codec_ctx {
     // consumer unpack (unpack.hip): control words, tile sums, per-frame lengths; the frames it holds
     DevBuf up;
     uint64_t up_frames = 0;
+    DevBuf uh;  // user-header columns: control words (verdict, count, tile counter)
     DevBuf cwk;  // disk-chunk walk: state, gates, per-batch slice results, fragments
     // multi-record decode (decode_records.hip): tasks | states | wg map, block sums,
     // results, and the pinned staging of the task table (uploaded in one copy)

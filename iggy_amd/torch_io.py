@@ -115,6 +115,91 @@ def unpack_record(cx, d_record, integrity: int = 0, cursor=None) -> dict:
     return r
 
 
+def header_columns(cx, d_record, keys, integrity: int = 0) -> dict:
+    """Decode the device-resident record `d_record` (a uint8 CUDA tensor), validate every
+    message's user headers and project the requested keys into per-message columns
+    (iggy_codec_user_headers_device): decode and columns are enqueued back to back on the
+    current stream, then ONE synchronise.
+
+    keys: up to 16 (kind, key bytes) pairs, kind an abi.KIND_* code. Returns a dict of
+    tensors trimmed to the record's `count` messages: `status` [count, 4] int32 (kind,
+    reason, offset, detail of iggy_header_status), `pairs` [count] int32, and `columns`, one
+    dict per key with `value_kinds` [count] uint8 (0 = absent), `value_lengths` [count]
+    uint8, `value_pos` [count] int32 and `values16` [count, 16] uint8 (the value's bytes as
+    stored, zero-padded); plus `count`, `with_headers`, `invalid_messages`, `first_invalid`
+    (None if every message is valid) and `found` (one count per key).
+
+    A fixed-size value is read by viewing its column, e.g. an Int64 / Uint64 / Float64 key:
+        col["values16"].view(torch.int64)[:, 0]      # (.view(torch.float64) for Float64)
+    and an Int32 key: col["values16"].view(torch.int32)[:, 0]; rows where value_kinds is 0
+    (absent key, or invalid headers) hold zeros.
+
+    The arrays form runs over what unpack_record wrote, e.g. several records chained with
+    one cursor (an int64 CUDA tensor of 4) and one call over all of them:
+        parts = [unpack_record(cx, r, cursor=cursor) for r in records]
+        # with `uh`, `starts` the whole user_headers / user_headers_starts arrays
+        cx.user_headers_arrays_device(uh.data_ptr(), starts.data_ptr(), cursor.data_ptr(),
+                                      cap, q, d_result.data_ptr(), stream)
+    (the cursor's first word is its `messages`, read on the device).
+    Raises CodecError carrying the wire error when the record does not decode."""
+    import ctypes
+
+    import torch
+
+    from . import abi
+    from .codec import CodecError
+
+    if d_record.dtype != torch.uint8 or not d_record.is_cuda or not d_record.is_contiguous():
+        raise ValueError("d_record must be a contiguous uint8 CUDA tensor")
+    keys = list(keys)
+    if len(keys) > abi.HEADER_MAX_KEYS:
+        raise ValueError("at most 16 keys")
+    n = d_record.numel()
+    dev = d_record.device
+    cap = n // 48 + 1
+
+    def arr(shape, dtype):
+        return torch.empty(shape, dtype=dtype, device=dev)
+
+    status, pairs = arr((cap, 4), torch.int32), arr((cap,), torch.int32)
+    cols = [{"value_kinds": arr((cap,), torch.uint8), "value_lengths": arr((cap,), torch.uint8),
+             "value_pos": arr((cap,), torch.int32), "values16": arr((cap, 16), torch.uint8)} for _ in keys]
+    q = abi.HeaderColumns()
+    q.cap_messages, q.nkeys = cap, len(keys)
+    q.status, q.pairs = status.data_ptr(), pairs.data_ptr()
+    for k, (kind, key) in enumerate(keys):
+        q.keys[k] = abi.HeaderKey.make(kind, key)
+        q.columns[k] = abi.HeaderColumn(*(cols[k][f].data_ptr() for f in ("value_kinds", "value_lengths",
+                                                                           "value_pos", "values16")))
+    d_pos = arr((cap,), torch.int64)
+    d_dec = torch.zeros(ctypes.sizeof(abi.DecodeResult), dtype=torch.uint8, device=dev)
+    d_res = torch.zeros(ctypes.sizeof(abi.HeaderColumnsResult), dtype=torch.uint8, device=dev)
+    cur = torch.cuda.current_stream(dev)  # (stream handling as unpack_record)
+    work = cur if cur.cuda_stream else torch.cuda.ExternalStream(cx.stream(), device=dev)
+    if work is not cur:
+        work.wait_stream(cur)
+    s = work.cuda_stream
+    rc = cx.decode_device(d_record.data_ptr(), n, integrity, d_pos.data_ptr(), cap, d_dec.data_ptr(), s)
+    if rc:
+        raise CodecError(rc, None, "header_columns: decode")
+    rc = cx.user_headers_device(d_record.data_ptr(), n, d_pos.data_ptr(), d_dec.data_ptr(), q, d_res.data_ptr(), s)
+    if rc:
+        raise CodecError(rc, None, "header_columns: user headers")
+    if work is not cur:
+        cur.wait_stream(work)
+    res = abi.HeaderColumnsResult.from_buffer_copy(to_host(d_res).tobytes())  # the one synchronise
+    if res.error.kind != abi.OK:
+        raise CodecError(res.error.kind, res.error, "header_columns")
+    c = res.count
+    return {
+        "count": c, "with_headers": res.with_headers, "invalid_messages": res.invalid_messages,
+        "first_invalid": None if res.first_invalid == 2**64 - 1 else res.first_invalid,
+        "found": [res.found[k] for k in range(len(keys))],
+        "status": status[:c], "pairs": pairs[:c],
+        "columns": [{f: t[:c] for f, t in col.items()} for col in cols],
+    }
+
+
 def to_host(t) -> np.ndarray:
     """A numpy copy of tensor `t` (synchronous; the copy lands in pinned memory)."""
     import torch

@@ -89,6 +89,11 @@ typedef enum iggy_error_kind {
      * (core/message_bus/src/framing.rs:165-171) */
     IGGY_ERR_CONNECTION_CLOSED = 25,
     IGGY_ERR_TCP_ERROR = 26,
+    /* IggyError::InvalidHeaderKey (4018) / InvalidHeaderValue (4019) / InvalidHeaderKind
+     * (4040) of the user-header domain decode (common/src/wire_conversions.rs:802-840) */
+    IGGY_ERR_INVALID_HEADER_KEY = 27,
+    IGGY_ERR_INVALID_HEADER_VALUE = 28,
+    IGGY_ERR_INVALID_HEADER_KIND = 29,      /* reason = the offending kind code */
     /* library-level failures (not wire errors) */
     IGGY_ERR_DEVICE = 100,
     IGGY_ERR_INVALID_ARGUMENT = 101,
@@ -111,7 +116,11 @@ typedef enum iggy_validation_reason {
     IGGY_V_STRING_ID_EMPTY = 7,      /* "string identifier cannot be empty"                     identifier.rs:215-219 */
     IGGY_V_BALANCED_LENGTH = 8,      /* "balanced partitioning must have length 0, got {a}"     partitioning.rs:111-115 */
     IGGY_V_PARTITION_ID_LENGTH = 9,  /* "partition_id partitioning must have length 4, got {a}" partitioning.rs:119-123 */
-    IGGY_V_MESSAGES_KEY_EMPTY = 10   /* "messages_key partitioning cannot have empty key"       partitioning.rs:128-132 */
+    IGGY_V_MESSAGES_KEY_EMPTY = 10,  /* "messages_key partitioning cannot have empty key"       partitioning.rs:128-132 */
+    /* user-header TLV walk (binary_protocol/src/primitives/user_headers.rs) */
+    IGGY_V_HEADER_KIND_ZERO = 11,    /* "header kind is 0 (reserved) at offset {pos}"            user_headers.rs:94-98 */
+    IGGY_V_HEADER_FIELD_LENGTH = 12, /* "header field length {n} out of range 1..=255 at offset" user_headers.rs:104-109 */
+    IGGY_V_HEADER_ODD_ENTRIES = 13   /* "odd number of TLV entries ({n}), expected key-value pairs" user_headers.rs:132-136 */
 } iggy_validation_reason;
 
 /* UnknownDiscriminant.type_name (error.rs:39-44) */
@@ -518,6 +527,128 @@ int iggy_codec_unpack_batch_device(iggy_codec_ctx *ctx, const uint8_t *d_record,
                                    const uint64_t *d_frame_pos, const iggy_decode_result *d_decode,
                                    const iggy_unpacked_messages *out, iggy_unpack_cursor *d_cursor /* nullable */,
                                    iggy_unpack_result *d_result, void *stream);
+
+/* ------------------------------------------------------------ user headers */
+/* The second half of the consumer decode: every message's user headers validated with
+ * the reference's verdict, and up to 16 requested keys projected into per-message
+ * columns -- the device form of IggyMessage::user_headers_map / get_user_header
+ * (common/src/types/message/iggy_message.rs:238-297).
+ *
+ * Wire form (binary_protocol/src/primitives/user_headers.rs:18-27):
+ *   [key_kind u8][key_len u32 LE][key][val_kind u8][val_len u32 LE][val]  repeated.
+ *
+ * Stage 1, structural (validate_user_headers, user_headers.rs:84-139), from byte 0 while
+ * pos < len, per TLV:
+ *   kind byte 0                      -> VALIDATION / IGGY_V_HEADER_KIND_ZERO, offset = pos       (:93-98)
+ *   the u32 length does not fit      -> UNEXPECTED_EOF, offset = pos + 1, need 4                 (:101, codec.rs:110-124)
+ *   length 0 or above 255            -> VALIDATION / IGGY_V_HEADER_FIELD_LENGTH, offset = pos + 1,
+ *                                       detail = the length                                      (:104-109)
+ *   the data passes the end          -> UNEXPECTED_EOF, offset = data start, need = length        (:116-122)
+ *   after the walk an odd TLV count  -> VALIDATION / IGGY_V_HEADER_ODD_ENTRIES, detail = count    (:132-136)
+ *   an empty buffer is valid with 0 pairs (:85-87); kind codes 16..255 pass this stage (:40-47).
+ * Stage 2, domain (headers_from_validated_slice with UnknownKinds::Reject,
+ * common/src/wire_conversions.rs:802-840), only when the WHOLE buffer passed stage 1 (so a
+ * structural error anywhere wins over a domain error in an earlier pair); per pair, in
+ * walk order, the first failing pair ends the decode:
+ *   key kind not in 1..15            -> INVALID_HEADER_KIND, reason = key kind        (:811-822)
+ *   else value kind not in 1..15     -> INVALID_HEADER_KIND, reason = value kind      (:811-822)
+ *   else fixed-size key kind, other length   -> INVALID_HEADER_KEY                    (:823-827)
+ *   else fixed-size value kind, other length -> INVALID_HEADER_VALUE                  (:828-832)
+ *   sizes (HeaderKind::expected_size, common/src/types/message/user_headers.rs:272-281;
+ *   codes :231-247): Raw 1 / String 2 any 1..255; Bool 3, Int8 4, Uint8 9: 1; Int16 5,
+ *   Uint16 10: 2; Int32 6, Uint32 11, Float32 14: 4; Int64 7, Uint64 12, Float64 15: 8;
+ *   Int128 8, Uint128 13: 16.
+ * Lookup: the map is a BTreeMap filled with insert (wire_conversions.rs:834-837), so for a
+ * repeated key the LAST pair wins; key identity is (kind code, key bytes); a message whose
+ * headers fail either stage has no map (iggy_message.rs:238-297): every key is absent. */
+#define IGGY_HEADER_MAX_KEYS 16u
+#define IGGY_HEADER_MAX_KEY_BYTES 1024u  /* summed key lengths of one call (the keys travel with the launch) */
+
+typedef struct iggy_header_key {  /* host memory */
+    uint8_t kind;                 /* 1..15 */
+    uint8_t length;               /* 1..255; the kind's fixed size for a fixed-size kind */
+    uint8_t bytes[255];
+    uint8_t _pad[7];
+} iggy_header_key;
+
+typedef struct iggy_header_status {  /* 16 B per message */
+    uint32_t kind;    /* IGGY_OK, IGGY_ERR_UNEXPECTED_EOF, IGGY_ERR_VALIDATION, IGGY_ERR_INVALID_HEADER_* */
+    uint32_t reason;  /* iggy_validation_reason; for INVALID_HEADER_KIND the offending code */
+    uint32_t offset;  /* structural: the offset the reference reports (0 for the odd count);
+                         domain: the offset of the failing pair's key-kind byte */
+    uint32_t detail;  /* EOF: need (have = length - offset); field length: the length found;
+                         odd entries: the TLV count; otherwise 0 */
+} iggy_header_status;
+
+/* One requested key's columns. DEVICE pointers, any may be NULL (= not wanted). */
+typedef struct iggy_header_column {
+    uint8_t  *value_kinds;    /* [cap] 0 = absent, else the value's kind code                        */
+    uint8_t  *value_lengths;  /* [cap]                                                               */
+    uint32_t *value_pos;      /* [cap] byte offset of the value's data inside the message's headers  */
+    uint8_t  *values16;       /* [cap][16] the value's bytes as stored (little-endian), zero-padded;
+                                 the first 16 B of a longer String / Raw value. Absent: zeros.      */
+} iggy_header_column;
+
+typedef struct iggy_header_columns {  /* host struct */
+    uint64_t cap_messages;
+    uint32_t nkeys;                   /* 0..16; 0 = validate only */
+    uint32_t _pad;
+    iggy_header_key keys[IGGY_HEADER_MAX_KEYS];
+    iggy_header_column columns[IGGY_HEADER_MAX_KEYS];
+    iggy_header_status *status;       /* [cap] device, nullable */
+    uint32_t *pairs;                  /* [cap] device, nullable: key/value pairs, 0 on any error */
+} iggy_header_columns;
+
+typedef struct iggy_header_columns_result {  /* device memory */
+    iggy_wire_error error;      /* OK, the decode's own error, INVALID_ARGUMENT, or CAPACITY (a = count) */
+    uint64_t count;             /* messages looked at (0 on any error)                                  */
+    uint64_t with_headers;      /* messages whose headers are non-empty                                 */
+    uint64_t invalid_messages;  /* messages whose status is not OK                                      */
+    uint64_t first_invalid;     /* lowest such message index, UINT64_MAX if none                        */
+    uint64_t found[IGGY_HEADER_MAX_KEYS]; /* messages where key k is present                            */
+} iggy_header_columns_result;
+
+/* Record form: the user headers of the record that iggy_codec_decode_batch_device decoded
+ * into d_frame_pos / *d_decode; it chains after the decode exactly as the unpack does.
+ * Message i's headers are the user_headers_length bytes after the payload of the frame
+ * at 256 + d_frame_pos[i]; the count is d_decode->frame_count, read on the device.
+ * Enqueue-only on `stream` (two launches whatever the count, the grid sized from len).
+ *  - a failed or non-final decode: d_result->error is that error (INVALID_ARGUMENT for a
+ *    result that is not final or does not fit len), count = 0, no output array is written.
+ *  - count > cap_messages: IGGY_ERR_CAPACITY with a = count, count = 0, nothing is written,
+ *    no counter is published. Nothing outside [0, count) of any array is ever written.
+ *  - *d_result is fully written on the stream in every case.
+ * Returns IGGY_ERR_INVALID_ARGUMENT synchronously for a null ctx, record, decode, q or
+ * result, len < 256, no d_frame_pos for a record with a body, nkeys > 16, a key of length
+ * 0, a key kind outside 1..15, a fixed-size key kind with another length, or key bytes
+ * above 1024 in total. Repeated request keys are legal (equal columns). */
+int iggy_codec_user_headers_device(iggy_codec_ctx *ctx, const uint8_t *d_record, uint64_t len,
+                                   const uint64_t *d_frame_pos, const iggy_decode_result *d_decode,
+                                   const iggy_header_columns *q, iggy_header_columns_result *d_result,
+                                   void *stream);
+
+/* Arrays form: over what the unpack (one record or a cursor chain) wrote. Message i's
+ * headers are d_user_headers[starts[i] .. starts[i + 1]) (spans below 4 GiB); *d_count is
+ * read on the device (for example &cursor->messages); cap_messages_hint only sizes the
+ * grid (any count is processed). The rest is as above; null d_user_headers_starts or
+ * d_count is refused synchronously (d_user_headers may be NULL only if every span is
+ * empty). */
+int iggy_codec_user_headers_arrays_device(iggy_codec_ctx *ctx, const uint8_t *d_user_headers,
+                                          const uint64_t *d_user_headers_starts, const uint64_t *d_count,
+                                          uint64_t cap_messages_hint, const iggy_header_columns *q,
+                                          iggy_header_columns_result *d_result, void *stream);
+
+/* Host twin (pure C++, user_headers.cpp; no device, no context): the same verdicts for a
+ * host-side consumer and for records too small to be worth a launch.
+ * iggy_user_headers_validate: both stages over buf[0, len); *pairs (nullable) = the pair
+ * count (0 on any error), *st (nullable) = the status. Returns st->kind.
+ * iggy_user_headers_get: the lookup of one key (get_user_header): *value_kind = 0 when the
+ * key is absent or the headers are invalid, else the value's kind, *value_pos its data
+ * offset in buf, *value_len its length (out-parameters nullable). Returns st->kind, or
+ * IGGY_ERR_INVALID_ARGUMENT for a null or malformed key (as the device entry refuses it). */
+int iggy_user_headers_validate(const uint8_t *buf, uint64_t len, uint32_t *pairs, iggy_header_status *st);
+int iggy_user_headers_get(const uint8_t *buf, uint64_t len, const iggy_header_key *key, uint8_t *value_kind,
+                          uint32_t *value_pos, uint8_t *value_len, iggy_header_status *st);
 
 /* ------------------------------------------------- server admission / prepare */
 /* PrepareHeader.size (u32) sits at byte 48 of the 256-B consensus header

@@ -453,6 +453,63 @@ assert ctypes.sizeof(HeaderColumns) == 16 + 16 * 264 + 16 * 32 + 16
 assert ctypes.sizeof(HeaderColumnsResult) == 192
 
 
+# ---- select (include/iggy_codec.h "select")
+SELECT_MAX_CLAUSES = 8
+(SEL_OFFSET, SEL_TIMESTAMP, SEL_ORIGIN_TIMESTAMP, SEL_PAYLOAD_LENGTH, SEL_USER_HEADERS_LENGTH, SEL_ID, SEL_HEADER,
+ SEL_HEADER_STATUS) = range(1, 9)
+(OP_EQ, OP_NE, OP_LT, OP_LE, OP_GT, OP_GE, OP_PRESENT, OP_ABSENT) = range(1, 9)
+
+
+class SelectClause(ctypes.Structure):
+    """iggy_select_clause: one typed clause (host memory; the column / status pointers are
+    device pointers for the device entry, host pointers for the host twin)."""
+    _fields_ = [("source", u32), ("op", u32), ("kind", ctypes.c_uint8), ("length", ctypes.c_uint8),
+                ("_pad", ctypes.c_uint8 * 6), ("operand", ctypes.c_uint8 * 16), ("column", HeaderColumn),
+                ("status", ctypes.c_void_p)]
+
+    @classmethod
+    def make(cls, source: int, op: int = 0, operand: bytes = b"", kind: int = 0, column: HeaderColumn | None = None,
+             status: int | None = None, length: int | None = None) -> "SelectClause":
+        """(no check here: the entry points refuse a malformed clause). operand: the
+        little-endian bytes (at most 16); length defaults to len(operand)."""
+        x = cls()
+        operand = bytes(operand)[:16]
+        x.source, x.op, x.kind = source, op, kind
+        x.length = len(operand) if length is None else length
+        ctypes.memmove(x.operand, operand, len(operand))
+        if column is not None:
+            x.column = column
+        x.status = status
+        return x
+
+
+class SelectSpec(ctypes.Structure):
+    """iggy_select_spec: up to 8 ANDed clauses and an optional mask."""
+    _fields_ = [("nclauses", u32), ("_pad", u32), ("d_mask", ctypes.c_void_p),
+                ("clauses", SelectClause * SELECT_MAX_CLAUSES)]
+
+    @classmethod
+    def make(cls, clauses=(), mask: int | None = None) -> "SelectSpec":
+        x = cls()
+        clauses = list(clauses)
+        x.nclauses, x.d_mask = len(clauses), mask
+        for k, c in enumerate(clauses[:SELECT_MAX_CLAUSES]):
+            x.clauses[k] = c
+        return x
+
+
+class SelectResult(ctypes.Structure):
+    """iggy_select_result: the device-resident outcome of one select."""
+    _fields_ = [("error", WireError), ("examined", u64), ("count", u64), ("payload_bytes", u64),
+                ("user_headers_bytes", u64), ("first_message", u64), ("min_payload_length", u32),
+                ("max_payload_length", u32)]
+
+
+assert ctypes.sizeof(SelectClause) == 72
+assert ctypes.sizeof(SelectSpec) == 16 + 8 * 72
+assert ctypes.sizeof(SelectResult) == 80
+
+
 class PollFragment(ctypes.Structure):
     """iggy_poll_fragment: one host span of a poll reply (PollFragments)."""
     _fields_ = [("data", ctypes.c_void_p), ("len", u64)]

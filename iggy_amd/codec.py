@@ -116,6 +116,8 @@ def load(path: str) -> ctypes.CDLL:
     L.iggy_codec_user_headers_arrays_device.argtypes = [vp, vp, vp, vp, u64, vp, vp, vp]
     L.iggy_user_headers_validate.argtypes = [vp, u64, vp, vp]
     L.iggy_user_headers_get.argtypes = [vp, u64, vp, vp, vp, vp, vp]
+    L.iggy_codec_select_messages_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.iggy_select_mask_host.argtypes = [vp, u64, vp, vp]
     L.iggy_codec_decode_prepare.argtypes = [vp, vp, u64, ci, vp, vp]
     L.iggy_codec_admit_batch.argtypes = [vp, vp, u64, u32, u64, ci, vp, u64, vp, vp]
     L.iggy_codec_recover_segment.argtypes = [vp, vp, u64, u64, vp]
@@ -501,6 +503,16 @@ class Codec:
                                                              d_count, cap_messages_hint, ctypes.byref(q),
                                                              d_result, stream)
 
+    def select_messages_device(self, src: abi.UnpackedMessages, d_count: int, spec: abi.SelectSpec,
+                               out: abi.UnpackedMessages, d_source_index: int | None, d_out_cursor: int | None,
+                               d_result: int, stream: int | None = None) -> int:
+        """iggy_codec_select_messages_device: the messages [0, *d_count) of `src` that pass
+        `spec`, compacted in source order into the arrays of `out` (device pointers). Enqueue
+        only; the result is an abi.SelectResult at d_result."""
+        return self._L.iggy_codec_select_messages_device(self._h, ctypes.byref(src), d_count, ctypes.byref(spec),
+                                                         ctypes.byref(out), d_source_index, d_out_cursor, d_result,
+                                                         stream)
+
     # --------------------------------------------------------- device buffers
     def decode_device(self, d_body: int, length: int, integrity: int, d_frame_pos: int | None,
                       cap: int, d_result: int, stream: int | None = None) -> int:
@@ -597,6 +609,15 @@ class Codec:
 
 
 PAGE = 4096
+
+
+def select_mask_host(src: abi.UnpackedMessages, count: int, spec: abi.SelectSpec):
+    """iggy_select_mask_host (no device, no context): the keep verdict of `spec` for the
+    messages [0, count) of `src`, whose arrays, like the spec's columns, status and mask, are
+    HOST pointers -> (rc, uint8 array of count verdicts)."""
+    keep = np.zeros(max(count, 1), dtype=np.uint8)
+    rc = lib().iggy_select_mask_host(ctypes.byref(src), count, ctypes.byref(spec), keep.ctypes.data)
+    return rc, keep[:count]
 
 
 def host_buffer(shape, dtype=np.uint8) -> np.ndarray:

@@ -235,6 +235,9 @@ struct iggy_codec_ctx {
     DevBuf up;
     uint64_t up_frames = 0;
     DevBuf uh;  // user-header columns: control words (verdict, count, tile counter)
+    // select (select.hip): control words, tile sums, source index, keep flags; the messages it holds
+    DevBuf sel;
+    uint64_t sel_messages = 0;
     DevBuf cwk;  // disk-chunk walk: state, gates, per-batch slice results, fragments
     // multi-record decode (decode_records.hip): tasks | states | wg map, block sums,
     // results, and the pinned staging of the task table (uploaded in one copy)

@@ -110,6 +110,7 @@ def unpack_record(cx, d_record, integrity: int = 0, cursor=None) -> dict:
     r["payloads"] = t["payloads"][bp:bp + res.payload_bytes]
     r["user_headers"] = t["user_headers"][bu:bu + res.user_headers_bytes]
     r["count"], r["first_message"] = c, f
+    r["payload_base"], r["user_headers_base"] = bp, bu  # where the (absolute) starts begin
     if c and res.min_payload_length == res.max_payload_length:
         r["payloads_2d"] = r["payloads"].view(c, res.max_payload_length)
     return r
@@ -198,6 +199,133 @@ def header_columns(cx, d_record, keys, integrity: int = 0) -> dict:
         "status": status[:c], "pairs": pairs[:c],
         "columns": [{f: t[:c] for f, t in col.items()} for col in cols],
     }
+
+
+_SEL_SOURCES = {"offset": 1, "timestamp": 2, "origin_timestamp": 3, "payload_length": 4, "user_headers_length": 5,
+                "id": 6}
+_SEL_OPS = {"==": 1, "!=": 2, "<": 3, "<=": 4, ">": 5, ">=": 6, "present": 7, "absent": 8}
+_SEL_KIND_SIZE = {3: 1, 4: 1, 5: 2, 6: 4, 7: 8, 8: 16, 9: 1, 10: 2, 11: 4, 12: 8, 13: 16, 14: 4, 15: 8}
+
+
+def select_clause(source, op=None, value=None, kind: int = 0):
+    """One abi.SelectClause for select_messages.
+
+    source: "offset", "timestamp", "origin_timestamp", "payload_length", "user_headers_length" or
+    "id" with op one of "==", "!=", "<", "<=", ">", ">=" and an int value; or one column dict of
+    header_columns()["columns"] with a compare op, the value's `kind` (abi.KIND_*) and the value
+    (an int for the integer kinds and Bool, a float for the float kinds, bytes as stored
+    otherwise), or with op "present" / "absent"; or the `status` tensor of header_columns()
+    (no op: true where the headers are valid)."""
+    import struct
+
+    from . import abi
+    if isinstance(source, str):
+        width = 16 if source == "id" else 8
+        return abi.SelectClause.make(_SEL_SOURCES[source], _SEL_OPS[op],
+                                     (int(value) % (1 << (8 * width))).to_bytes(width, "little"))
+    if not isinstance(source, dict):
+        return abi.SelectClause.make(abi.SEL_HEADER_STATUS, status=source.data_ptr())
+    col = abi.HeaderColumn(source["value_kinds"].data_ptr(), source["value_lengths"].data_ptr(), None,
+                           source["values16"].data_ptr())
+    if op in ("present", "absent"):
+        return abi.SelectClause.make(abi.SEL_HEADER, _SEL_OPS[op], column=col)
+    if isinstance(value, float):
+        value = struct.pack("<f" if kind == abi.KIND_FLOAT32 else "<d", value)
+    elif isinstance(value, int):
+        size = _SEL_KIND_SIZE[kind]
+        value = (value % (1 << (8 * size))).to_bytes(size, "little")
+    return abi.SelectClause.make(abi.SEL_HEADER, _SEL_OPS[op], bytes(value), kind, col)
+
+
+def select_messages(cx, arrays: dict, clauses=(), mask=None, cursor=None) -> dict:
+    """Keep the messages of `arrays` (the dict unpack_record returns) that pass every clause
+    (select_clause(...) or abi.SelectClause objects, at most 8) and whose `mask` entry (an
+    optional uint8 CUDA tensor of `count`) is nonzero, compacted in source order
+    (iggy_codec_select_messages_device): enqueued on the current stream with the stream
+    handling of unpack_record, then ONE synchronise.
+
+    Outputs are allocated at the source's capacities. Returns the arrays of unpack_record
+    trimmed to the kept `count`, plus `source_index` [count] (int64: which source message each
+    kept one was, to gather header columns or other per-message tensors), `first_message`,
+    `examined`, and `raw`, an abi.RawMessages of the kept messages for Codec.encode_device.
+
+    cursor: as unpack_record's (an int64 CUDA tensor of 4 that this call advances), so that
+    selects and unpacks append into one numbering; the returned tensors are this call's part.
+    Raises CodecError carrying the wire error of a failed select."""
+    import ctypes
+
+    import torch
+
+    from . import abi
+    from .codec import CodecError
+
+    n = int(arrays["count"])
+    dev = arrays["payloads"].device
+    names = ("ids", "checksums", "offsets", "timestamps", "origin_timestamps", "payload_lengths",
+             "user_headers_lengths", "payload_starts", "user_headers_starts", "payloads", "user_headers")
+    for k in names:
+        if not arrays[k].is_cuda or not arrays[k].is_contiguous():
+            raise ValueError(f"arrays[{k!r}] must be a contiguous CUDA tensor")
+    sp, su = int(arrays.get("payload_base", 0)), int(arrays.get("user_headers_base", 0))
+    np_, nu = arrays["payloads"].numel(), arrays["user_headers"].numel()
+    # (the starts are absolute positions: the byte arrays' bases are their positions 0)
+    # (an empty byte array has no address: it is left out of the source and of the output)
+    empty = {k for k in ("payloads", "user_headers") if arrays[k].numel() == 0}
+    src = abi.UnpackedMessages(n, sp + np_, su + nu, *(
+        None if k in empty else arrays[k].data_ptr() - (sp if k == "payloads" else su if k == "user_headers" else 0)
+        for k in names))
+    bm = bp = bu = 0
+    if cursor is not None:
+        bm, bp, bu = (int(x) for x in to_host(cursor)[:3])
+
+    def arr(k, dtype):
+        return torch.empty(max(k, 1), dtype=dtype, device=dev)
+
+    i64 = torch.int64
+    t = {
+        "ids": arr(2 * (bm + n), i64), "checksums": arr(bm + n, i64), "offsets": arr(bm + n, i64),
+        "timestamps": arr(bm + n, i64), "origin_timestamps": arr(bm + n, i64),
+        "payload_lengths": arr(bm + n, torch.int32), "user_headers_lengths": arr(bm + n, torch.int32),
+        "payload_starts": arr(bm + n + 1, i64), "user_headers_starts": arr(bm + n + 1, i64),
+        "payloads": arr(bp + np_, torch.uint8), "user_headers": arr(bu + nu, torch.uint8),
+    }
+    out = abi.UnpackedMessages(bm + n, bp + np_, bu + nu, *(None if k in empty else t[k].data_ptr() for k in names))
+    d_idx = arr(bm + n, i64)
+    d_cnt = to_device(np.array([n], dtype=np.int64), dev)
+    d_res = torch.zeros(ctypes.sizeof(abi.SelectResult), dtype=torch.uint8, device=dev)
+    spec = abi.SelectSpec.make(list(clauses), mask.data_ptr() if mask is not None else None)
+    cur = torch.cuda.current_stream(dev)  # (stream handling as unpack_record)
+    work = cur if cur.cuda_stream else torch.cuda.ExternalStream(cx.stream(), device=dev)
+    if work is not cur:
+        work.wait_stream(cur)
+    rc = cx.select_messages_device(src, d_cnt.data_ptr(), spec, out, d_idx.data_ptr(),
+                                   cursor.data_ptr() if cursor is not None else None, d_res.data_ptr(),
+                                   work.cuda_stream)
+    if rc:
+        raise CodecError(rc, None, "select_messages")
+    if work is not cur:
+        cur.wait_stream(work)
+    res = abi.SelectResult.from_buffer_copy(to_host(d_res).tobytes())  # the one synchronise
+    if res.error.kind != abi.OK:
+        raise CodecError(res.error.kind, res.error, "select_messages")
+    c, f = res.count, res.first_message
+    r = {k: t[k][f:f + c] for k in ("checksums", "offsets", "timestamps", "origin_timestamps",
+                                    "payload_lengths", "user_headers_lengths")}
+    r["ids"] = t["ids"][2 * f:2 * (f + c)].view(c, 2)
+    r["payload_starts"] = t["payload_starts"][f:f + c + 1]
+    r["user_headers_starts"] = t["user_headers_starts"][f:f + c + 1]
+    r["payloads"] = t["payloads"][bp:bp + res.payload_bytes]
+    r["user_headers"] = t["user_headers"][bu:bu + res.user_headers_bytes]
+    r["source_index"] = d_idx[f:f + c]
+    r["count"], r["first_message"], r["examined"] = c, f, res.examined
+    r["payload_base"], r["user_headers_base"] = bp, bu
+    r["raw"] = abi.RawMessages(c, r["ids"].data_ptr(), r["origin_timestamps"].data_ptr(), r["payloads"].data_ptr(),
+                               r["payload_lengths"].data_ptr(),
+                               r["user_headers"].data_ptr() if res.user_headers_bytes else None,
+                               r["user_headers_lengths"].data_ptr())
+    if c and res.min_payload_length == res.max_payload_length:
+        r["payloads_2d"] = r["payloads"].view(c, res.max_payload_length)
+    return r
 
 
 def to_host(t) -> np.ndarray:

@@ -650,6 +650,142 @@ int iggy_user_headers_validate(const uint8_t *buf, uint64_t len, uint32_t *pairs
 int iggy_user_headers_get(const uint8_t *buf, uint64_t len, const iggy_header_key *key, uint8_t *value_kind,
                           uint32_t *value_pos, uint8_t *value_len, iggy_header_status *st);
 
+/* ------------------------------------------------------------ select (filter, re-batch) */
+/* The step between "I have columns" and "I encode what I want": a small conjunction of
+ * typed clauses over the per-message arrays of an iggy_unpacked_messages and over header
+ * columns (iggy_header_column / iggy_header_status), ANDed with an optional caller mask,
+ * and the surviving messages compacted, in source order, into a second set of
+ * iggy_unpacked_messages arrays (again an iggy_raw_messages for
+ * iggy_codec_encode_batch_device). The kept count stays on the device, so decode ->
+ * unpack -> user headers -> select -> encode queue back to back with no host wait.
+ *
+ * Clause semantics (the library's own: the reference has typed header accessors,
+ * common/src/types/message/user_headers.rs, but no ordering):
+ *  - IGGY_SEL_OFFSET / TIMESTAMP / ORIGIN_TIMESTAMP (u64 arrays of the source),
+ *    IGGY_SEL_PAYLOAD_LENGTH / USER_HEADERS_LENGTH (u32 arrays), IGGY_SEL_ID (u128: id_lo,
+ *    id_hi): unsigned compare with the operand's low 8 / 4 / 16 bytes (little-endian);
+ *    kind and length are not read.
+ *  - IGGY_SEL_HEADER with a compare op (EQ, NE, LT, LE, GT, GE): FALSE when the key is
+ *    absent (value_kinds[i] == 0) or its kind differs from the operand's kind, under every
+ *    compare op, NE included. Otherwise, by kind, on the first `length` bytes of values16:
+ *      Int8..Int128, Uint8..Uint128: as sign- or zero-extended 128-bit integers;
+ *      Bool: EQ and NE, on the byte;
+ *      Float32 / Float64: IEEE order, -0 equals +0, a NaN on either side makes every op
+ *        false except NE; decided on the bit pattern with integer instructions only, so
+ *        denormal modes cannot change a verdict;
+ *      String / Raw: EQ and NE; equal means value_lengths[i] == length and the first
+ *        `length` bytes of values16 match (a stored value longer than 16 bytes therefore
+ *        never equals an operand).
+ *  - IGGY_SEL_HEADER with PRESENT / ABSENT: value_kinds[i] != 0 / == 0, whatever the kind
+ *    (kind, length and operand are not read).
+ *  - IGGY_SEL_HEADER_STATUS: true when status[i].kind == IGGY_OK (op, kind, length and
+ *    operand are not read).
+ * A message is kept iff the mask, if any, is nonzero for it and every clause is true. */
+#define IGGY_SELECT_MAX_CLAUSES 8u
+
+#define IGGY_SEL_OFFSET 1u
+#define IGGY_SEL_TIMESTAMP 2u
+#define IGGY_SEL_ORIGIN_TIMESTAMP 3u
+#define IGGY_SEL_PAYLOAD_LENGTH 4u
+#define IGGY_SEL_USER_HEADERS_LENGTH 5u
+#define IGGY_SEL_ID 6u
+#define IGGY_SEL_HEADER 7u
+#define IGGY_SEL_HEADER_STATUS 8u
+
+#define IGGY_OP_EQ 1u
+#define IGGY_OP_NE 2u
+#define IGGY_OP_LT 3u
+#define IGGY_OP_LE 4u
+#define IGGY_OP_GT 5u
+#define IGGY_OP_GE 6u
+#define IGGY_OP_PRESENT 7u  /* IGGY_SEL_HEADER only */
+#define IGGY_OP_ABSENT 8u   /* IGGY_SEL_HEADER only */
+
+typedef struct iggy_select_clause {  /* host memory, travels by value with the launch; 72 B */
+    uint32_t source;                  /* IGGY_SEL_*                                                     */
+    uint32_t op;                      /* IGGY_OP_*                                                      */
+    uint8_t  kind;                    /* IGGY_SEL_HEADER compare: the header value kind 1..15 of the operand */
+    uint8_t  length;                  /* operand bytes used: String / Raw 1..16, else the kind's size   */
+    uint8_t  _pad[6];
+    uint8_t  operand[16];             /* little-endian, as values16 stores it; u64 / u32 sources: low bytes */
+    iggy_header_column column;        /* IGGY_SEL_HEADER: value_kinds, value_lengths (String / Raw),
+                                         values16 (compare ops); value_pos is not read                   */
+    const iggy_header_status *status; /* IGGY_SEL_HEADER_STATUS                                          */
+} iggy_select_clause;
+
+typedef struct iggy_select_spec {    /* host struct */
+    uint32_t nclauses;                /* 0..8, ANDed; 0 = mask only (or keep everything)                */
+    uint32_t _pad;
+    const uint8_t *d_mask;            /* nullable: message i is a candidate iff d_mask[i] != 0          */
+    iggy_select_clause clauses[IGGY_SELECT_MAX_CLAUSES];
+} iggy_select_spec;
+
+typedef struct iggy_select_result {  /* device memory; 80 B */
+    iggy_wire_error error;            /* OK, INVALID_ARGUMENT (count above the source capacity), CAPACITY */
+    uint64_t examined;                /* *d_count as read                                               */
+    uint64_t count;                   /* messages kept (0 on any error)                                 */
+    uint64_t payload_bytes, user_headers_bytes;  /* of the kept messages (0 on any error)               */
+    uint64_t first_message;           /* index of the first kept message in the output arrays           */
+    uint32_t min_payload_length, max_payload_length;  /* of the kept messages (0, 0 when none)          */
+} iggy_select_result;
+
+/* Selects among src's messages [0, *d_count) and compacts the kept ones into *out. src and
+ * out are host structs of DEVICE pointers, the spec's column / status / mask pointers are
+ * device pointers, *d_count, *d_out_cursor and *d_result are device memory. Everything is
+ * enqueued on `stream` (no synchronisation; five launches whatever the count, at most:
+ * the two byte copies only for a wanted payloads / user_headers).
+ *  - Source and count: *d_count is read on the device (for example &cursor->messages after
+ *    an unpack chain, or &unpack_result->count). src->cap_messages bounds it and, with the
+ *    byte capacities, sizes the grids and the scratch. *d_count > src->cap_messages:
+ *    d_result->error is IGGY_ERR_INVALID_ARGUMENT (a = the count), count = 0, nothing else
+ *    is written, the cursor stays.
+ *  - Copying is per array: any array of out may be NULL (= not wanted); an array wanted in
+ *    out needs the same array in src. payloads (user_headers) wanted in out need
+ *    payload_starts (user_headers_starts) in src AND in out. A kept message's payload /
+ *    user-header length is src's payload_lengths / user_headers_lengths entry when that
+ *    array is present, else the difference of its two src starts (below 4 GiB), else 0.
+ *  - Stable: kept messages appear in source order; positions come from prefix sums alone,
+ *    so the output is bit-identical from run to run.
+ *  - Placement is the unpack's: with d_out_cursor (nullable; bases 0 without) kept messages
+ *    land at message index cursor.messages, kept bytes at cursor.payload_bytes /
+ *    cursor.user_headers_bytes; the *_starts hold absolute positions and entry
+ *    [first_message + count] is written; the cursor advances on success only. Several
+ *    selects, and unpacks, can therefore append into one set of arrays.
+ *  - d_source_index (nullable, out->cap_messages entries): entry [first_message + j] is the
+ *    source index of kept message j, to gather the caller's own per-message tensors.
+ *  - Capacity is checked on the device before any byte is copied: first_message + count >
+ *    out->cap_messages, or the kept payload (user-header) total with the cursor's base above
+ *    cap_payload_bytes (cap_user_headers_bytes) when that array is wanted, gives
+ *    IGGY_ERR_CAPACITY with a = messages, b = payload bytes, c = user-header bytes needed
+ *    (bases included); count = 0, no output array is written, the cursor stays. Nothing
+ *    beyond a capacity is ever written.
+ *  - 16-B loads of the byte copies stay below the end of the last kept message's source
+ *    bytes; nothing outside [base, base + total) of an output byte array is written.
+ *  - out must not overlap src: identical pointers for a wanted array are refused
+ *    synchronously, any other overlap is undefined.
+ * Returns IGGY_ERR_INVALID_ARGUMENT synchronously for a null ctx, src, d_count, spec, out
+ * or result; nclauses > 8; an unknown source or op; PRESENT or ABSENT on a non-header
+ * source; a clause whose source array (in src, its column, or its status) is NULL; a header
+ * operand kind outside 1..15; a length that is not the kind's fixed size; a String or Raw
+ * length outside 1..16; an ordering op (LT, LE, GT, GE) on String, Raw or Bool; an array
+ * wanted in out and missing in src (or equal to it); payloads / user_headers without their
+ * starts. Scratch is the context's (9 B per message of src->cap_messages;
+ * iggy_codec_reserve(.., max_frames) sizes it; a larger source grows it outside the stream
+ * order, as the unpack's). */
+int iggy_codec_select_messages_device(iggy_codec_ctx *ctx, const iggy_unpacked_messages *src,
+                                      const uint64_t *d_count, const iggy_select_spec *spec,
+                                      const iggy_unpacked_messages *out, uint64_t *d_source_index /* nullable */,
+                                      iggy_unpack_cursor *d_out_cursor /* nullable */,
+                                      iggy_select_result *d_result, void *stream);
+
+/* Host twin (pure C++, select.cpp; no device, no context): the clause verdicts alone, for
+ * small host-side consumers. src, the spec's columns, status and mask are HOST pointers;
+ * keep_out[i] = 1 when message i of [0, count) is kept, else 0. The same synchronous
+ * refusals as the device entry's for the spec (plus a null keep_out, and count >
+ * src->cap_messages); returns 0 otherwise. */
+int iggy_select_mask_host(const iggy_unpacked_messages *src, uint64_t count, const iggy_select_spec *spec,
+                          uint8_t *keep_out);
+
 /* ------------------------------------------------- server admission / prepare */
 /* PrepareHeader.size (u32) sits at byte 48 of the 256-B consensus header
  * (binary_protocol/src/consensus/header.rs:901-932); the batch header follows it. */

@@ -510,6 +510,42 @@ assert ctypes.sizeof(SelectSpec) == 16 + 8 * 72
 assert ctypes.sizeof(SelectResult) == 80
 
 
+# ---- route (include/iggy_codec.h "route")
+ROUTE_MAX_PARTITIONS = 256
+ROUTE_DROP = 0xFFFFFFFF
+(ROUTE_KEY_ID, ROUTE_KEY_HEADER, ROUTE_KEY_BYTES, ROUTE_KEY_PARTITION) = range(1, 5)
+
+
+class RouteSpec(ctypes.Structure):
+    """iggy_route_spec: the partition count, the key source and its arrays (device pointers
+    for the device entry, host pointers for the host twin), an optional mask."""
+    _fields_ = [("partitions", u32), ("key_source", u32), ("absent_partition", u32), ("key_length", u32),
+                ("key_stride", u64), ("d_keys", ctypes.c_void_p), ("d_partition_ids", ctypes.c_void_p),
+                ("column", HeaderColumn), ("d_mask", ctypes.c_void_p)]
+
+    @classmethod
+    def make(cls, partitions: int, key_source: int, absent_partition: int = ROUTE_DROP, keys: int | None = None,
+             key_length: int = 0, key_stride: int = 0, partition_ids: int | None = None,
+             column: HeaderColumn | None = None, mask: int | None = None) -> "RouteSpec":
+        """(no check here: the entry points refuse a malformed spec)"""
+        x = cls()
+        x.partitions, x.key_source, x.absent_partition = partitions, key_source, absent_partition
+        x.key_length, x.key_stride, x.d_keys, x.d_partition_ids, x.d_mask = key_length, key_stride, keys, partition_ids, mask
+        if column is not None:
+            x.column = column
+        return x
+
+
+class RouteResult(ctypes.Structure):
+    """iggy_route_result: the device-resident outcome of one route."""
+    _fields_ = [("error", WireError), ("examined", u64), ("count", u64), ("dropped", u64), ("payload_bytes", u64),
+                ("user_headers_bytes", u64), ("partitions", u32), ("_pad", u32)]
+
+
+assert ctypes.sizeof(RouteSpec) == 80
+assert ctypes.sizeof(RouteResult) == 80
+
+
 class PollFragment(ctypes.Structure):
     """iggy_poll_fragment: one host span of a poll reply (PollFragments)."""
     _fields_ = [("data", ctypes.c_void_p), ("len", u64)]

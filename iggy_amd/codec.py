@@ -118,6 +118,10 @@ def load(path: str) -> ctypes.CDLL:
     L.iggy_user_headers_get.argtypes = [vp, u64, vp, vp, vp, vp, vp]
     L.iggy_codec_select_messages_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.iggy_select_mask_host.argtypes = [vp, u64, vp, vp]
+    L.iggy_codec_route_messages_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.iggy_xxh32.argtypes = [vp, u64, u32]
+    L.iggy_xxh32.restype = u32
+    L.iggy_route_partitions_host.argtypes = [vp, u64, vp, vp]
     L.iggy_codec_decode_prepare.argtypes = [vp, vp, u64, ci, vp, vp]
     L.iggy_codec_admit_batch.argtypes = [vp, vp, u64, u32, u64, ci, vp, u64, vp, vp]
     L.iggy_codec_recover_segment.argtypes = [vp, vp, u64, u64, vp]
@@ -513,6 +517,20 @@ class Codec:
                                                          ctypes.byref(out), d_source_index, d_out_cursor, d_result,
                                                          stream)
 
+    def route_messages_device(self, src: abi.UnpackedMessages, d_count: int, spec: abi.RouteSpec,
+                              out: abi.UnpackedMessages | None, d_partition_first: int,
+                              d_partition_payload_first: int | None, d_partition_user_headers_first: int | None,
+                              d_partition_of: int | None, d_source_index: int | None, d_result: int,
+                              stream: int | None = None) -> int:
+        """iggy_codec_route_messages_device: the messages [0, *d_count) of `src` routed by
+        XXH32(key) % partitions and written into the arrays of `out` ordered by (partition,
+        source index), with the [partitions + 1] tables (out None: the partitions alone).
+        Enqueue only; the result is an abi.RouteResult at d_result."""
+        return self._L.iggy_codec_route_messages_device(
+            self._h, ctypes.byref(src), d_count, ctypes.byref(spec), ctypes.byref(out) if out is not None else None,
+            d_partition_first, d_partition_payload_first, d_partition_user_headers_first, d_partition_of,
+            d_source_index, d_result, stream)
+
     # --------------------------------------------------------- device buffers
     def decode_device(self, d_body: int, length: int, integrity: int, d_frame_pos: int | None,
                       cap: int, d_result: int, stream: int | None = None) -> int:
@@ -618,6 +636,22 @@ def select_mask_host(src: abi.UnpackedMessages, count: int, spec: abi.SelectSpec
     keep = np.zeros(max(count, 1), dtype=np.uint8)
     rc = lib().iggy_select_mask_host(ctypes.byref(src), count, ctypes.byref(spec), keep.ctypes.data)
     return rc, keep[:count]
+
+
+def xxh32(data, seed: int = 0) -> int:
+    """iggy_xxh32 (no device, no context): XXH32 of `data` (bytes-like); the reference's
+    calculate_32(key) is xxh32(key, 0)."""
+    b = bytes(data)
+    return lib().iggy_xxh32(b, len(b), seed)
+
+
+def route_partitions_host(src: abi.UnpackedMessages, count: int, spec: abi.RouteSpec):
+    """iggy_route_partitions_host (no device, no context): the partition of `spec` for the
+    messages [0, count) of `src`, whose arrays, like the spec's column, keys, partition ids
+    and mask, are HOST pointers -> (rc, uint32 array: the partition, abi.ROUTE_DROP = dropped)."""
+    part = np.zeros(max(count, 1), dtype=np.uint32)
+    rc = lib().iggy_route_partitions_host(ctypes.byref(src), count, ctypes.byref(spec), part.ctypes.data)
+    return rc, part[:count]
 
 
 def host_buffer(shape, dtype=np.uint8) -> np.ndarray:

@@ -39,6 +39,7 @@
 #include "unpack.hip"
 #include "user_headers.hip"
 #include "select.hip"
+#include "route.hip"
 static_assert(!IGGY_ENC_SPLIT || iggy::kErWaves == 4, "the writer-wave split is built for 4 hasher waves");
 
 using namespace iggy;
@@ -68,6 +69,7 @@ using namespace iggy;
 //   host_unpack   consumer unpack (struct-of-arrays output)
 //   host_user_headers  user-header validation and key columns
 //   host_select   device-side select (filter, stable compaction)
+//   host_route    device-side route (partition by key hash, stable N-way split)
 //   host_async    asynchronous submit / poll / wait
 #include "host_ctx.hpp"
 #include "host_mem.hpp"
@@ -81,6 +83,7 @@ using namespace iggy;
 #include "host_unpack.hpp"
 #include "host_user_headers.hpp"
 #include "host_select.hpp"
+#include "host_route.hpp"
 #include "host_async.hpp"
 
 
@@ -216,7 +219,7 @@ void iggy_codec_destroy(iggy_codec_ctx *c) {
                       &c->gbsums, &c->dresult, &c->din, &c->dpos, &c->dout, &c->epl, &c->euh,
                       &c->etile, &c->ecs, &c->emisc, &c->eids, &c->eots, &c->epay, &c->eplen,
                       &c->euhb, &c->euhl, &c->erec, &c->esink, &c->hbsums, &c->ppos, &c->pmsgs, &c->pres, &c->cwk, &c->sl, &c->slres, &c->cr,
-                      &c->rtab, &c->rbsums, &c->rres, &c->clinks, &c->rstate, &c->rcount, &c->pbres, &c->up, &c->uh, &c->sel};
+                      &c->rtab, &c->rbsums, &c->rres, &c->clinks, &c->rstate, &c->rcount, &c->pbres, &c->up, &c->uh, &c->sel, &c->rt};
     for (DevBuf *b : bufs) b->release();
     if (c->h_pinned) (void)hipHostFree(c->h_pinned);
     if (c->pb_pinned) (void)hipHostFree(c->pb_pinned);
@@ -268,8 +271,10 @@ int iggy_codec_reserve(iggy_codec_ctx *c, uint64_t max_batch_bytes, uint64_t max
     bind(c, nullptr);
     if (int r = ensure_decode_scratch(c, max_batch_bytes)) return r;
     if (int r = ensure_unpack_scratch(c, max_batch_bytes)) return r;
-    // the select's scratch is per message of its source's capacity
-    return max_frames ? ensure_select_scratch(c, max_frames) : 0;
+    // the select's and the route's scratch are per message of their source's capacity
+    if (!max_frames) return 0;
+    if (int r = ensure_select_scratch(c, max_frames)) return r;
+    return ensure_route_scratch(c, max_frames);
 }
 
 void *iggy_codec_stream(iggy_codec_ctx *c) { return c ? (void *)c->stream : nullptr; }

@@ -238,6 +238,10 @@ struct iggy_codec_ctx {
     // select (select.hip): control words, tile sums, source index, keep flags; the messages it holds
     DevBuf sel;
     uint64_t sel_messages = 0;
+    // route (route.hip): control words, tile sums, partition counts, source index, lengths in
+    // destination order, partitions; the messages it holds
+    DevBuf rt;
+    uint64_t rt_messages = 0;
     DevBuf cwk;  // disk-chunk walk: state, gates, per-batch slice results, fragments
     // multi-record decode (decode_records.hip): tasks | states | wg map, block sums,
     // results, and the pinned staging of the task table (uploaded in one copy)

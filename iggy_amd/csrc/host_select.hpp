@@ -72,13 +72,13 @@ int iggy_codec_select_messages_device(iggy_codec_ctx *c, const iggy_unpacked_mes
     hipLaunchKernelGGL(k_sel_fields, dim3(gtiles), dim3(256), 0, s, *src, *out, d_source_index, ss);
     if (out->payloads) {
         const uint64_t spans = std::min(out->cap_payload_bytes, src->cap_payload_bytes) / kUpSpan + 2;
-        hipLaunchKernelGGL(k_sel_copy, dim3((uint32_t)std::min(spans, wgs)), dim3(256), 0, s,
+        hipLaunchKernelGGL(k_sel_copy<true>, dim3((uint32_t)std::min(spans, wgs)), dim3(256), 0, s,
                            (const uint8_t *)src->payloads, (const uint64_t *)src->payload_starts,
                            (const uint64_t *)out->payload_starts, out->payloads, 0u, ss);
     }
     if (out->user_headers) {
         const uint64_t spans = std::min(out->cap_user_headers_bytes, src->cap_user_headers_bytes) / kUpSpan + 2;
-        hipLaunchKernelGGL(k_sel_copy, dim3((uint32_t)std::min(spans, wgs)), dim3(256), 0, s,
+        hipLaunchKernelGGL(k_sel_copy<true>, dim3((uint32_t)std::min(spans, wgs)), dim3(256), 0, s,
                            (const uint8_t *)src->user_headers, (const uint64_t *)src->user_headers_starts,
                            (const uint64_t *)out->user_headers_starts, out->user_headers, 1u, ss);
     }

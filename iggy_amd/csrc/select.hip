@@ -262,6 +262,9 @@ __global__ __launch_bounds__(256) void k_sel_fields(iggy_unpacked_messages src, 
 // starts = the destination's starts (absolute positions in dst, entry [first + kept] = end),
 // dst = the whole output array. Source of destination byte g of kept message m:
 // sbytes + sstarts[sidx[m]] + (g - starts[first + m]).
+// kSourceOrder: the kept messages are in source order (the select). false (the route,
+// route.hip): any order, the wide loads are bounded by the source's used bytes instead.
+template <bool kSourceOrder = true>
 __global__ __launch_bounds__(256) void k_sel_copy(const uint8_t *__restrict__ sbytes,
                                                   const uint64_t *__restrict__ sstarts,
                                                   const uint64_t *__restrict__ starts, uint8_t *__restrict__ dst,
@@ -277,7 +280,8 @@ __global__ __launch_bounds__(256) void k_sel_copy(const uint8_t *__restrict__ sb
     const uint64_t *st = starts + ss.ctl[kSelFirst];
     // wide (16-B) loads of a boundary piece stay below the end of the last kept message's
     // source bytes (kept messages are in source order: it is the highest byte read at all)
-    const uint64_t src_end = sstarts[ss.sidx[n - 1]] + (st[n] - st[n - 1]);
+    const uint64_t src_end =
+        kSourceOrder ? sstarts[ss.sidx[n - 1]] + (st[n] - st[n - 1]) : sstarts[ss.ctl[kSelExamined]];
     // 16-B chunks of the destination ADDRESS space: chunk 0 holds the array's first byte
     const uint64_t lead = (uint64_t)((uintptr_t)(dst + base) & 15);
     const uint64_t nchunks = (lead + tot + 15) / 16;

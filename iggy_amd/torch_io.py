@@ -328,6 +328,136 @@ def select_messages(cx, arrays: dict, clauses=(), mask=None, cursor=None) -> dic
     return r
 
 
+def route_messages(cx, arrays: dict, partitions: int, key="id", mask=None, absent=None) -> dict:
+    """Route the messages of `arrays` (the dict unpack_record, select_messages or this
+    function returns) to `partitions` (1..256) partitions by the reference's rule,
+    XXH32(key) % partitions, and group them per partition, stable inside a partition
+    (iggy_codec_route_messages_device): enqueued on the current stream with the stream
+    handling of unpack_record, then ONE synchronise.
+
+    key: "id" (the 16 id bytes, messages_key_u128(id)); ("header", column) with one column
+    dict of header_columns()["columns"] (the whole stored value is the key; a message without
+    it goes to partition `absent`, or is dropped when `absent` is None); ("bytes", tensor)
+    with a [count, L] uint8 CUDA tensor of fixed-length keys, L in 1..255 (its row stride is
+    the key stride); ("partition", tensor) with an int32 CUDA tensor of partition indices,
+    used as they are (>= partitions: dropped). mask: an optional uint8 CUDA tensor of `count`;
+    a message whose entry is zero is dropped.
+
+    Returns the arrays of unpack_record holding the routed `count` messages ordered by
+    (partition, source index), plus `partition_first`, `partition_payload_first`,
+    `partition_user_headers_first` (host lists of partitions + 1), `partition_of` [examined]
+    (int32 CUDA tensor, -1 = dropped), `source_index` [count], `examined`, `dropped`,
+    `partitions`, and `raw(p)`, the abi.RawMessages of partition p for Codec.encode_device.
+    Raises CodecError carrying the wire error of a failed route."""
+    import ctypes
+
+    import torch
+
+    from . import abi
+    from .codec import CodecError
+
+    n = int(arrays["count"])
+    dev = arrays["payloads"].device
+    names = ("ids", "checksums", "offsets", "timestamps", "origin_timestamps", "payload_lengths",
+             "user_headers_lengths", "payload_starts", "user_headers_starts", "payloads", "user_headers")
+    for k in names:
+        if not arrays[k].is_cuda or not arrays[k].is_contiguous():
+            raise ValueError(f"arrays[{k!r}] must be a contiguous CUDA tensor")
+    sp, su = int(arrays.get("payload_base", 0)), int(arrays.get("user_headers_base", 0))
+    np_, nu = arrays["payloads"].numel(), arrays["user_headers"].numel()
+    # (as select_messages: the starts are absolute, an empty byte array is left out)
+    empty = {k for k in ("payloads", "user_headers") if arrays[k].numel() == 0}
+    src = abi.UnpackedMessages(n, sp + np_, su + nu, *(
+        None if k in empty else arrays[k].data_ptr() - (sp if k == "payloads" else su if k == "user_headers" else 0)
+        for k in names))
+    d_mask = mask.data_ptr() if mask is not None else None
+    drop = abi.ROUTE_DROP if absent is None else int(absent)
+    keep = None  # (tensors the spec points at)
+    if key == "id":
+        spec = abi.RouteSpec.make(partitions, abi.ROUTE_KEY_ID, mask=d_mask)
+    elif key[0] == "header":
+        col = key[1]
+        if "user_headers" in empty:  # no header bytes at all: every key is absent, nothing is read
+            keep = torch.zeros(16, dtype=torch.uint8, device=dev)
+            src.user_headers = keep.data_ptr()
+        spec = abi.RouteSpec.make(partitions, abi.ROUTE_KEY_HEADER, drop, mask=d_mask, column=abi.HeaderColumn(
+            col["value_kinds"].data_ptr(), col["value_lengths"].data_ptr(), col["value_pos"].data_ptr(), None))
+    elif key[0] == "bytes":
+        keep = key[1]
+        if keep.dtype != torch.uint8 or keep.dim() != 2 or keep.stride(1) != 1 or keep.shape[0] < n:
+            raise ValueError("bytes keys must be a [count, L] uint8 CUDA tensor with unit inner stride")
+        spec = abi.RouteSpec.make(partitions, abi.ROUTE_KEY_BYTES, keys=keep.data_ptr(), key_length=keep.shape[1],
+                                  key_stride=keep.stride(0), mask=d_mask)
+    elif key[0] == "partition":
+        keep = key[1]
+        if keep.dtype != torch.int32 or not keep.is_contiguous() or keep.numel() < n:
+            raise ValueError("partition ids must be a contiguous int32 CUDA tensor of count")
+        spec = abi.RouteSpec.make(partitions, abi.ROUTE_KEY_PARTITION, partition_ids=keep.data_ptr(), mask=d_mask)
+    else:
+        raise ValueError("key must be 'id', ('header', column), ('bytes', tensor) or ('partition', tensor)")
+
+    def arr(k, dtype):
+        return torch.empty(max(k, 1), dtype=dtype, device=dev)
+
+    i64 = torch.int64
+    t = {
+        "ids": arr(2 * n, i64), "checksums": arr(n, i64), "offsets": arr(n, i64), "timestamps": arr(n, i64),
+        "origin_timestamps": arr(n, i64), "payload_lengths": arr(n, torch.int32),
+        "user_headers_lengths": arr(n, torch.int32), "payload_starts": arr(n + 1, i64),
+        "user_headers_starts": arr(n + 1, i64), "payloads": arr(np_, torch.uint8), "user_headers": arr(nu, torch.uint8),
+    }
+    out = abi.UnpackedMessages(n, np_, nu, *(None if k in empty else t[k].data_ptr() for k in names))
+    npart = max(int(partitions), 0) + 1
+    d_tab = torch.zeros((3, npart), dtype=i64, device=dev)  # first, payload first, user-headers first
+    d_of, d_idx = arr(n, torch.int32), arr(n, i64)
+    d_cnt = to_device(np.array([n], dtype=np.int64), dev)
+    d_res = torch.zeros(ctypes.sizeof(abi.RouteResult), dtype=torch.uint8, device=dev)
+    cur = torch.cuda.current_stream(dev)  # (stream handling as unpack_record)
+    work = cur if cur.cuda_stream else torch.cuda.ExternalStream(cx.stream(), device=dev)
+    if work is not cur:
+        work.wait_stream(cur)
+    rc = cx.route_messages_device(src, d_cnt.data_ptr(), spec, out, d_tab[0].data_ptr(), d_tab[1].data_ptr(),
+                                  d_tab[2].data_ptr(), d_of.data_ptr(), d_idx.data_ptr(), d_res.data_ptr(),
+                                  work.cuda_stream)
+    if rc:
+        raise CodecError(rc, None, "route_messages")
+    if work is not cur:
+        cur.wait_stream(work)
+    # the result and the three tables in one copy: the one synchronise
+    back = to_host(torch.cat([d_res, d_tab.view(torch.uint8).reshape(-1)]))
+    res = abi.RouteResult.from_buffer_copy(back[:d_res.numel()].tobytes())
+    if res.error.kind != abi.OK:
+        raise CodecError(res.error.kind, res.error, "route_messages")
+    tab = back[d_res.numel():].view(np.int64).reshape(3, npart)
+    c = res.count
+    r = {k: t[k][:c] for k in ("checksums", "offsets", "timestamps", "origin_timestamps", "payload_lengths",
+                               "user_headers_lengths")}
+    r["ids"] = t["ids"][:2 * c].view(c, 2)
+    r["payload_starts"], r["user_headers_starts"] = t["payload_starts"][:c + 1], t["user_headers_starts"][:c + 1]
+    r["payloads"], r["user_headers"] = t["payloads"][:res.payload_bytes], t["user_headers"][:res.user_headers_bytes]
+    r["source_index"], r["partition_of"] = d_idx[:c], d_of[:n]
+    r["count"], r["examined"], r["dropped"], r["partitions"] = c, res.examined, res.dropped, res.partitions
+    r["first_message"], r["payload_base"], r["user_headers_base"] = 0, 0, 0
+    first, pfirst, ufirst = (tab[k].tolist() for k in range(3))
+    if "payloads" in empty:
+        pfirst = [0] * npart
+    if "user_headers" in empty:
+        ufirst = [0] * npart
+    r["partition_first"], r["partition_payload_first"], r["partition_user_headers_first"] = first, pfirst, ufirst
+
+    def raw(p: int):
+        """The abi.RawMessages of partition p (offset pointers into the routed arrays)."""
+        a, b = first[p], first[p + 1]
+        uh = res.user_headers_bytes and ufirst[p + 1] > ufirst[p]
+        return abi.RawMessages(b - a, t["ids"].data_ptr() + 16 * a, t["origin_timestamps"].data_ptr() + 8 * a,
+                               t["payloads"].data_ptr() + pfirst[p], t["payload_lengths"].data_ptr() + 4 * a,
+                               t["user_headers"].data_ptr() + ufirst[p] if uh else None,
+                               t["user_headers_lengths"].data_ptr() + 4 * a)
+
+    r["raw"] = raw
+    return r
+
+
 def to_host(t) -> np.ndarray:
     """A numpy copy of tensor `t` (synchronous; the copy lands in pinned memory)."""
     import torch

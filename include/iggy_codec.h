@@ -786,6 +786,131 @@ int iggy_codec_select_messages_device(iggy_codec_ctx *ctx, const iggy_unpacked_m
 int iggy_select_mask_host(const iggy_unpacked_messages *src, uint64_t count, const iggy_select_spec *spec,
                           uint8_t *keep_out);
 
+/* ------------------------------------------------------------ route (partition by key hash) */
+/* The step after "I have the messages I want": which partition does each one go to, and the
+ * messages grouped per partition so that each group encodes as its own batch. The rule is
+ * the reference's for Partitioning::messages_key: calculate_32(key) % partition_count, with
+ * calculate_32 = XxHash32::oneshot(0, key) (core/common/src/utils/hash.rs:18-22; SDK side
+ * core/common/src/traits/binary_impls/messages.rs:154-164; server side
+ * core/metadata/src/stm/stream.rs:1303-1324); the key forms are those of
+ * core/common/src/types/message/partitioning.rs:84-128 (1..255 raw bytes, or a little-endian
+ * u32 / u64 / u128). One stable N-way split replaces N selects.
+ *
+ * Message i's partition is iggy_xxh32(key_i, key_len_i, 0) % partitions, the key by source:
+ *  - IGGY_ROUTE_KEY_ID: the 16 bytes of src->ids[2i], ids[2i + 1] (little-endian), which is
+ *    messages_key_u128(id).
+ *  - IGGY_ROUTE_KEY_HEADER: the WHOLE stored value of one header column's key,
+ *    src->user_headers[src->user_headers_starts[i] + value_pos[i] .. + value_lengths[i])
+ *    (1..255 B; not the 16-B column copy). A message with value_kinds[i] == 0 (the key is
+ *    absent, or the headers are invalid: "user headers" above) goes to absent_partition, or
+ *    is dropped when that is IGGY_ROUTE_DROP; so does a message whose (value_pos,
+ *    value_lengths) do not lie inside its own header bytes (a column of other messages).
+ *  - IGGY_ROUTE_KEY_BYTES: d_keys[i * key_stride .. + key_length), any address: covers
+ *    messages_key_u32 / _u64 and anything the caller computed.
+ *  - IGGY_ROUTE_KEY_PARTITION: d_partition_ids[i] as it is, no hashing; a value >=
+ *    partitions drops the message.
+ * A message is dropped when its mask byte is zero (its key is then not read), or for the
+ * absent and PARTITION cases above. No key load passes the key's last byte. */
+#define IGGY_ROUTE_MAX_PARTITIONS 256u
+#define IGGY_ROUTE_DROP 0xFFFFFFFFu
+
+#define IGGY_ROUTE_KEY_ID 1u
+#define IGGY_ROUTE_KEY_HEADER 2u
+#define IGGY_ROUTE_KEY_BYTES 3u
+#define IGGY_ROUTE_KEY_PARTITION 4u
+
+typedef struct iggy_route_spec {     /* host struct, travels by value with the launch; 80 B */
+    uint32_t partitions;             /* 1..256                                                          */
+    uint32_t key_source;             /* IGGY_ROUTE_KEY_*                                                */
+    uint32_t absent_partition;       /* HEADER: where a message without the key goes: < partitions, or
+                                        IGGY_ROUTE_DROP                                                 */
+    uint32_t key_length;             /* BYTES: 1..255                                                   */
+    uint64_t key_stride;             /* BYTES: >= key_length                                            */
+    const uint8_t  *d_keys;          /* BYTES                                                           */
+    const uint32_t *d_partition_ids; /* PARTITION                                                       */
+    iggy_header_column column;       /* HEADER: value_kinds, value_lengths, value_pos; values16 is not read */
+    const uint8_t  *d_mask;          /* nullable: message i is routed only if d_mask[i] != 0            */
+} iggy_route_spec;
+
+typedef struct iggy_route_result {   /* device memory; 80 B */
+    iggy_wire_error error;           /* OK, INVALID_ARGUMENT (count above the source capacity), CAPACITY */
+    uint64_t examined;               /* *d_count as read                                                */
+    uint64_t count, dropped;         /* routed, dropped: count + dropped == examined on success; 0, 0 on any error */
+    uint64_t payload_bytes, user_headers_bytes;  /* of the routed messages (0 on any error)             */
+    uint32_t partitions, _pad;
+} iggy_route_result;
+
+/* Routes src's messages [0, *d_count) and writes the routed ones into *out ordered by
+ * (partition, source index): stable inside a partition, no gaps, bases 0 (there is no
+ * cursor in this call). src / out are host structs of DEVICE pointers as the select's; the
+ * spec's pointers, *d_count, the tables and *d_result are device memory. Everything is
+ * enqueued on `stream` (no synchronisation; seven launches whatever the count, at most: the
+ * two byte copies only for a wanted payloads / user_headers, and three launches with out ==
+ * NULL).
+ *  - d_partition_first ([partitions + 1], required): entry [p] is the index in *out of
+ *    partition p's first message, entry [partitions] = count.
+ *    d_partition_payload_first / d_partition_user_headers_first ([partitions + 1], nullable;
+ *    each needs its starts array in out): the same for the bytes of payloads / user_headers,
+ *    that is out->payload_starts[d_partition_first[p]]. The encoder reads lengths, not starts,
+ *    so partition p is an iggy_raw_messages of offset pointers: count = first[p + 1] -
+ *    first[p], ids + 2 * first[p], payload_lengths + first[p], payloads + payload_first[p].
+ *  - d_partition_of (nullable, src->cap_messages entries, source order): message i's
+ *    partition, IGGY_ROUTE_DROP for a dropped one. d_source_index (nullable,
+ *    out->cap_messages entries, destination order; needs out): the source index of routed
+ *    message j.
+ *  - The per-array rules are the select's: any array of out may be NULL; a wanted array needs
+ *    its source; payloads / user_headers need their starts in src AND out; a length is src's
+ *    lengths entry, else the difference of its two src starts, else 0. payload_starts /
+ *    user_headers_starts of out are absolute with entry [count] written.
+ *  - out == NULL: hash only. d_partition_of, d_partition_first (the prefix sums of the
+ *    partition counts) and the result are produced; the two byte tables and d_source_index
+ *    must then be NULL.
+ *  - Errors, on the device, before any byte is copied: *d_count > src->cap_messages gives
+ *    IGGY_ERR_INVALID_ARGUMENT (a = the count) and nothing else is written. count >
+ *    out->cap_messages, or the routed payload (user-header) total above cap_payload_bytes
+ *    (cap_user_headers_bytes) when that array is wanted, gives IGGY_ERR_CAPACITY with a =
+ *    messages, b = payload bytes, c = user-header bytes needed, count = 0, and no output array
+ *    or table (d_partition_of included) is written. Nothing beyond a capacity is ever written,
+ *    nothing outside [0, total) of an output byte array.
+ *  - The destination order is not the source order: 16-B loads of the byte copies stay below
+ *    src's used bytes, src->payload_starts[*d_count] (user_headers_starts likewise).
+ *  - Deterministic: positions come from counts and prefix sums alone (integer sums, whose
+ *    value does not depend on their order); two runs give bit-identical outputs.
+ * Returns IGGY_ERR_INVALID_ARGUMENT synchronously for a null ctx, src, d_count, spec, result
+ * or d_partition_first; partitions outside 1..256; an unknown key source; absent_partition >=
+ * partitions when it is not IGGY_ROUTE_DROP; BYTES with a null array, key_length outside
+ * 1..255 or a stride below the length; PARTITION with a null array; HEADER with a null
+ * value_kinds, value_lengths or value_pos, or without src->user_headers_starts /
+ * src->user_headers; ID without src->ids; the select's refusals for out (an array wanted and
+ * missing in src or equal to it, a byte array without its starts); a byte table without its
+ * starts array in out; a byte table or d_source_index with out == NULL.
+ * Scratch is the context's: 18 B per message of src->cap_messages (source index 8 B, the two
+ * lengths in destination order 8 B, the partition 2 B), and per tile of 2048 messages 1 KiB
+ * of partition counts plus 16 B of byte sums, per 1024 destination messages 16 B;
+ * iggy_codec_reserve(.., max_frames) sizes it; a larger source grows it outside the stream
+ * order, as the select's. */
+int iggy_codec_route_messages_device(iggy_codec_ctx *ctx, const iggy_unpacked_messages *src,
+                                     const uint64_t *d_count, const iggy_route_spec *spec,
+                                     const iggy_unpacked_messages *out /* nullable: hash only */,
+                                     uint64_t *d_partition_first,
+                                     uint64_t *d_partition_payload_first /* nullable */,
+                                     uint64_t *d_partition_user_headers_first /* nullable */,
+                                     uint32_t *d_partition_of /* nullable */,
+                                     uint64_t *d_source_index /* nullable */,
+                                     iggy_route_result *d_result, void *stream);
+
+/* XXH32 of data[0, len) (pure host code, no context): the reference's calculate_32 is
+ * iggy_xxh32(key, len, 0). Restated from the published specification (xxh32.hpp). */
+uint32_t iggy_xxh32(const void *data, uint64_t len, uint32_t seed);
+
+/* Host twin (pure C++, route.cpp; no device, no context): the partitions alone. src, the
+ * spec's column, keys, partition ids and mask are HOST pointers; partition_of_out[i] is
+ * message i's partition or IGGY_ROUTE_DROP for [0, count). The device entry's synchronous
+ * refusals for the spec (plus a null partition_of_out, and count > src->cap_messages);
+ * returns 0 otherwise. */
+int iggy_route_partitions_host(const iggy_unpacked_messages *src, uint64_t count, const iggy_route_spec *spec,
+                               uint32_t *partition_of_out);
+
 /* ------------------------------------------------- server admission / prepare */
 /* PrepareHeader.size (u32) sits at byte 48 of the 256-B consensus header
  * (binary_protocol/src/consensus/header.rs:901-932); the batch header follows it. */

@@ -36,6 +36,7 @@
 #include "poll.hip"
 #include "slice.hip"
 #include "crypt.hip"
+#include "soa_common.hpp"  // shared by unpack.hip, select.hip and route.hip
 #include "unpack.hip"
 #include "user_headers.hip"
 #include "select.hip"

@@ -7,36 +7,35 @@
 
 namespace {
 
-// [0, 256) control words | source tile byte sums (2 x 8 B per tile of 2048) | destination
-// tile byte sums (2 x 8 B per 1024) | partition counts (256 x 4 B per tile) | source index
-// (8 B per message) | lengths in destination order (8 B) | partition (2 B)
-uint64_t route_tiles(uint64_t messages) { return messages / kRtTile + 2; }
-uint64_t route_dtiles(uint64_t messages) { return messages / kRtDTile + 2; }
+RouteScratch route_layout(Carve &cv, uint64_t messages) {
+    const uint64_t nt = messages / kRtTile + 2, nd = messages / kRtDTile + 2;
+    RouteScratch rs;
+    rs.ctl = cv.take<uint64_t>(256);  // (control words: 8 used)
+    rs.tile_pl = cv.take<uint64_t>(nt * 8);
+    rs.tile_uh = cv.take<uint64_t>(nt * 8);
+    rs.dtile_pl = cv.take<uint64_t>(nd * 8);
+    rs.dtile_uh = cv.take<uint64_t>(nd * 8);
+    rs.hist = cv.take<uint32_t>(nt * kRtParts * 4);
+    rs.sidx = cv.take<uint64_t>(messages * 8);
+    rs.dlens = cv.take<uint2>(messages * 8);
+    rs.part = cv.take<uint16_t>(messages * 2);
+    rs.max_messages = messages;
+    return rs;
+}
 
 int ensure_route_scratch(iggy_codec_ctx *c, uint64_t messages) {
     messages = std::max<uint64_t>(messages, 1);
     if (messages <= c->rt_messages && c->rt.p) return 0;
-    const uint64_t nt = route_tiles(messages), nd = route_dtiles(messages);
-    if (c->rt.ensure(256 + nt * 16 + nd * 16 + nt * kRtParts * 4 + messages * 18)) return IGGY_ERR_DEVICE;
+    Carve size{nullptr};
+    route_layout(size, messages);
+    if (c->rt.ensure(size.at)) return IGGY_ERR_DEVICE;
     c->rt_messages = messages;
     return 0;
 }
 
 RouteScratch rscratch(iggy_codec_ctx *c) {
-    const uint64_t nt = route_tiles(c->rt_messages), nd = route_dtiles(c->rt_messages), m = c->rt_messages;
-    RouteScratch rs;
-    uint64_t at = 0;
-    rs.ctl = c->rt.as<uint64_t>(at), at += 256;
-    rs.tile_pl = c->rt.as<uint64_t>(at), at += nt * 8;
-    rs.tile_uh = c->rt.as<uint64_t>(at), at += nt * 8;
-    rs.dtile_pl = c->rt.as<uint64_t>(at), at += nd * 8;
-    rs.dtile_uh = c->rt.as<uint64_t>(at), at += nd * 8;
-    rs.hist = c->rt.as<uint32_t>(at), at += nt * kRtParts * 4;
-    rs.sidx = c->rt.as<uint64_t>(at), at += m * 8;
-    rs.dlens = c->rt.as<uint2>(at), at += m * 8;
-    rs.part = c->rt.as<uint16_t>(at);
-    rs.max_messages = m;
-    return rs;
+    Carve cv{c->rt.as<uint8_t>()};
+    return route_layout(cv, c->rt_messages);
 }
 
 }  // namespace
@@ -85,22 +84,11 @@ int iggy_codec_route_messages_device(iggy_codec_ctx *c, const iggy_unpacked_mess
         hipLaunchKernelGGL(k_route_starts, dim3(gd), dim3(256), 0, s, o, prog.partitions,
                            (const uint64_t *)d_partition_first, d_partition_payload_first,
                            d_partition_user_headers_first, rs);
-        SelScratch ss{};  // the copy reads the control words and the source index alone
-        ss.ctl = rs.ctl;
-        ss.sidx = rs.sidx;
-        ss.max_messages = rs.max_messages;
-        if (out->payloads) {
-            const uint64_t spans = std::min(out->cap_payload_bytes, src->cap_payload_bytes) / kUpSpan + 2;
-            hipLaunchKernelGGL(k_sel_copy<false>, dim3((uint32_t)std::min(spans, wgs)), dim3(256), 0, s,
-                               (const uint8_t *)src->payloads, (const uint64_t *)src->payload_starts,
-                               (const uint64_t *)out->payload_starts, out->payloads, 0u, ss);
-        }
-        if (out->user_headers) {
-            const uint64_t spans = std::min(out->cap_user_headers_bytes, src->cap_user_headers_bytes) / kUpSpan + 2;
-            hipLaunchKernelGGL(k_sel_copy<false>, dim3((uint32_t)std::min(spans, wgs)), dim3(256), 0, s,
-                               (const uint8_t *)src->user_headers, (const uint64_t *)src->user_headers_starts,
-                               (const uint64_t *)out->user_headers_starts, out->user_headers, 1u, ss);
-        }
+        using Source = SoaIndexedSource<false>;
+        launch_copies(s, wgs, *out, rs.ctl, Source{src->payloads, src->payload_starts, rs.sidx},
+                      std::min(out->cap_payload_bytes, src->cap_payload_bytes),
+                      Source{src->user_headers, src->user_headers_starts, rs.sidx},
+                      std::min(out->cap_user_headers_bytes, src->cap_user_headers_bytes));
     }
     HIP_OK(hipGetLastError());
     return 0;

@@ -7,29 +7,33 @@
 
 namespace {
 
-// [0, 256) control words | tile sums (kept, payload, user headers) | tile min / max |
-// source index (8 B per message) | keep flags (1 B per message)
+SelScratch select_layout(Carve &cv, uint64_t messages) {
+    const uint64_t ntiles = messages / kSelTile + 2;
+    SelScratch ss;
+    ss.ctl = cv.take<uint64_t>(256);  // (control words: 8 used)
+    ss.tile_n = cv.take<uint64_t>(ntiles * 8);
+    ss.tile_pl = cv.take<uint64_t>(ntiles * 8);
+    ss.tile_uh = cv.take<uint64_t>(ntiles * 8);
+    ss.tile_mm = cv.take<uint32_t>(ntiles * 8);
+    ss.sidx = cv.take<uint64_t>(messages * 8);
+    ss.flags = cv.take<uint8_t>(messages);
+    ss.max_messages = messages;
+    return ss;
+}
+
 int ensure_select_scratch(iggy_codec_ctx *c, uint64_t messages) {
     messages = std::max<uint64_t>(messages, 1);
     if (messages <= c->sel_messages && c->sel.p) return 0;
-    const uint64_t ntiles = messages / kSelTile + 2;
-    if (c->sel.ensure(256 + ntiles * 32 + messages * 9)) return IGGY_ERR_DEVICE;
+    Carve size{nullptr};
+    select_layout(size, messages);
+    if (c->sel.ensure(size.at)) return IGGY_ERR_DEVICE;
     c->sel_messages = messages;
     return 0;
 }
 
 SelScratch sscratch(iggy_codec_ctx *c) {
-    const uint64_t ntiles = c->sel_messages / kSelTile + 2;
-    SelScratch ss;
-    ss.ctl = c->sel.as<uint64_t>(0);
-    ss.tile_n = c->sel.as<uint64_t>(256);
-    ss.tile_pl = c->sel.as<uint64_t>(256 + ntiles * 8);
-    ss.tile_uh = c->sel.as<uint64_t>(256 + ntiles * 16);
-    ss.tile_mm = c->sel.as<uint32_t>(256 + ntiles * 24);
-    ss.sidx = c->sel.as<uint64_t>(256 + ntiles * 32);
-    ss.flags = c->sel.as<uint8_t>(256 + ntiles * 32 + c->sel_messages * 8);
-    ss.max_messages = c->sel_messages;
-    return ss;
+    Carve cv{c->sel.as<uint8_t>()};
+    return select_layout(cv, c->sel_messages);
 }
 
 // an array wanted in out needs the same array in src, at another address
@@ -70,18 +74,11 @@ int iggy_codec_select_messages_device(iggy_codec_ctx *c, const iggy_unpacked_mes
     hipLaunchKernelGGL(k_sel_flags, dim3(gtiles), dim3(256), 0, s, *src, d_count, prog, ss);
     hipLaunchKernelGGL(k_sel_scan, dim3(1), dim3(256), 0, s, *src, d_count, *out, d_out_cursor, ss, d_result);
     hipLaunchKernelGGL(k_sel_fields, dim3(gtiles), dim3(256), 0, s, *src, *out, d_source_index, ss);
-    if (out->payloads) {
-        const uint64_t spans = std::min(out->cap_payload_bytes, src->cap_payload_bytes) / kUpSpan + 2;
-        hipLaunchKernelGGL(k_sel_copy<true>, dim3((uint32_t)std::min(spans, wgs)), dim3(256), 0, s,
-                           (const uint8_t *)src->payloads, (const uint64_t *)src->payload_starts,
-                           (const uint64_t *)out->payload_starts, out->payloads, 0u, ss);
-    }
-    if (out->user_headers) {
-        const uint64_t spans = std::min(out->cap_user_headers_bytes, src->cap_user_headers_bytes) / kUpSpan + 2;
-        hipLaunchKernelGGL(k_sel_copy<true>, dim3((uint32_t)std::min(spans, wgs)), dim3(256), 0, s,
-                           (const uint8_t *)src->user_headers, (const uint64_t *)src->user_headers_starts,
-                           (const uint64_t *)out->user_headers_starts, out->user_headers, 1u, ss);
-    }
+    using Source = SoaIndexedSource<true>;
+    launch_copies(s, wgs, *out, ss.ctl, Source{src->payloads, src->payload_starts, ss.sidx},
+                  std::min(out->cap_payload_bytes, src->cap_payload_bytes),
+                  Source{src->user_headers, src->user_headers_starts, ss.sidx},
+                  std::min(out->cap_user_headers_bytes, src->cap_user_headers_bytes));
     HIP_OK(hipGetLastError());
     return 0;
 }

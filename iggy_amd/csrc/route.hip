@@ -27,14 +27,15 @@
 //                   -> payload_starts / user_headers_starts (the output has no gaps), and the
 //                   two byte tables, starts[first[p]], by a search of each index in
 //                   d_partition_first staged in LDS.
-//  k_sel_copy<false> (select.hip): the select's byte copy with the wide loads bounded by
-//                   the end of the source's used bytes: the destination order is not the
-//                   source order here.
+//  k_soa_copy<SoaIndexedSource<false>> (soa_common.hpp): the byte copy the unpack and the
+//                   select share, with the wide loads bounded by the end of the source's
+//                   used bytes: the destination order is not the source order here.
 //
-// No position comes from an atomic's return value: the output is bit-identical from run to
-// run. Every kernel reads the source count from device memory; the host sizes the grids
+// The scans, the capacity verdict, the control words and the scatter of the fixed-width
+// arrays are soa_common.hpp's. No position comes from an atomic's return value: the output
+// is bit-identical from run to run. Every kernel reads the source count from device memory; the host sizes the grids
 // from the capacities alone.
-#include "codec_common.hpp"
+#include "soa_common.hpp"
 #include "route_key.hpp"
 
 namespace iggy {
@@ -45,10 +46,9 @@ constexpr uint32_t kRtPer = 4;
 constexpr uint32_t kRtDTile = 256 * kRtPer;    // destination messages per starts tile
 constexpr uint32_t kRtParts = IGGY_ROUTE_MAX_PARTITIONS;
 constexpr uint32_t kRtDrop = 0xFFFFu;          // a dropped message in RouteScratch::part
-// (control words [0, 8) are the select copy's kSel* words: k_sel_copy reads them)
 
 struct RouteScratch {
-    uint64_t *ctl;          // [8] kSel* words (first and the bases 0)
+    uint64_t *ctl;          // [8] kSoa* words (first and the bases 0), kSoaAux = the messages examined
     uint64_t *tile_pl;      // [ntiles] routed payload bytes per source tile
     uint64_t *tile_uh;      // [ntiles]
     uint64_t *dtile_pl;     // [ndtiles] payload bytes per destination tile -> tile offsets after k_route_dscan
@@ -60,16 +60,12 @@ struct RouteScratch {
     uint64_t max_messages;  // messages the scratch holds (>= the source's cap_messages)
 };
 
-__device__ __forceinline__ bool route_gate(uint64_t n, const iggy_unpacked_messages &src, const RouteScratch &rs) {
-    return n <= src.cap_messages && n <= rs.max_messages;
-}
-
 __global__ __launch_bounds__(256) void k_route_keys(iggy_unpacked_messages src, const uint64_t *d_count,
                                                     RouteProgram prog, RouteScratch rs) {
     __shared__ uint32_t s_hist[kRtParts];
     __shared__ uint64_t s_pl[256], s_uh[256];
     const uint64_t n = *d_count;
-    if (!route_gate(n, src, rs)) return;
+    if (!soa_gate(n, src, rs.max_messages)) return;
     const uint32_t tid = threadIdx.x;
     const uint64_t ntiles = (n + kRtTile - 1) / kRtTile;
     for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
@@ -83,21 +79,15 @@ __global__ __launch_bounds__(256) void k_route_keys(iggy_unpacked_messages src, 
                 rs.part[i] = (uint16_t)(p == IGGY_ROUTE_DROP ? kRtDrop : p);
                 if (p != IGGY_ROUTE_DROP) {
                     atomicAdd(&s_hist[p], 1u);
-                    pl += sel_len(src.payload_lengths, src.payload_starts, i);
-                    uh += sel_len(src.user_headers_lengths, src.user_headers_starts, i);
+                    pl += soa_len(src.payload_lengths, src.payload_starts, i);
+                    uh += soa_len(src.user_headers_lengths, src.user_headers_starts, i);
                 }
             }
         }
         s_pl[tid] = pl;
         s_uh[tid] = uh;
         __syncthreads();
-        for (uint32_t k = 128; k > 0; k >>= 1) {
-            if (tid < k) {
-                s_pl[tid] += s_pl[tid + k];
-                s_uh[tid] += s_uh[tid + k];
-            }
-            __syncthreads();
-        }
+        soa_reduce<false>(tid, nullptr, nullptr, s_pl, s_uh);
         if (tid < prog.partitions) rs.hist[t * prog.partitions + tid] = s_hist[tid];
         if (tid == 0) {
             rs.tile_pl[t] = s_pl[0];
@@ -113,7 +103,7 @@ __global__ __launch_bounds__(256) void k_route_scan(iggy_unpacked_messages src, 
     __shared__ uint64_t s_a[256], s_b[256];
     const uint32_t tid = threadIdx.x;
     const uint64_t n = *d_count;
-    if (!route_gate(n, src, rs)) {
+    if (!soa_gate(n, src, rs.max_messages)) {
         if (tid == 0) {
             iggy_route_result r{};
             r.error.kind = IGGY_ERR_INVALID_ARGUMENT;
@@ -121,7 +111,7 @@ __global__ __launch_bounds__(256) void k_route_scan(iggy_unpacked_messages src, 
             r.examined = n;
             r.partitions = partitions;
             *res = r;
-            rs.ctl[kSelOk] = 0;
+            rs.ctl[kSoaOk] = 0;
         }
         return;
     }
@@ -137,27 +127,17 @@ __global__ __launch_bounds__(256) void k_route_scan(iggy_unpacked_messages src, 
     s_a[tid] = pl;
     s_b[tid] = uh;
     __syncthreads();
-    for (uint32_t k = 128; k > 0; k >>= 1) {
-        if (tid < k) {
-            s_a[tid] += s_a[tid + k];
-            s_b[tid] += s_b[tid + k];
-        }
-        __syncthreads();
-    }
+    soa_reduce<false>(tid, nullptr, nullptr, s_a, s_b);
     const uint64_t tot_pl = s_a[0], tot_uh = s_b[0];
     __syncthreads();
     s_a[tid] = mine;
     __syncthreads();
-    for (uint32_t k = 1; k < 256; k <<= 1) {  // inclusive scan over the partitions (Hillis-Steele in LDS)
-        const uint64_t a = tid >= k ? s_a[tid - k] : 0;
-        __syncthreads();
-        s_a[tid] += a;
-        __syncthreads();
-    }
+    soa_scan(tid, s_a);  // over the partitions
     const uint64_t first = s_a[tid] - mine, count = s_a[255];
-    const bool fits = !has_out || (count <= o.cap_messages && (!o.payloads || tot_pl <= o.cap_payload_bytes) &&
-                                   (!o.user_headers || tot_uh <= o.cap_user_headers_bytes));
-    if (fits) {
+    // (no cursor: the output starts at 0; without an output there is nothing to fit)
+    SoaPlacement p = soa_place(nullptr, o, count, tot_pl, tot_uh);
+    p.fits = p.fits || !has_out;
+    if (p.fits) {
         if (tid < partitions) {
             pfirst[tid] = first;
             uint64_t run = first;  // (below 2^32: the host refuses a larger source capacity)
@@ -178,26 +158,16 @@ __global__ __launch_bounds__(256) void k_route_scan(iggy_unpacked_messages src, 
     iggy_route_result r{};
     r.examined = n;
     r.partitions = partitions;
-    if (fits) {
+    if (p.fits) {
         r.count = count;
         r.dropped = n - count;
         r.payload_bytes = tot_pl;
         r.user_headers_bytes = tot_uh;
     } else {
-        r.error.kind = IGGY_ERR_CAPACITY;
-        r.error.a = count;
-        r.error.b = tot_pl;
-        r.error.c = tot_uh;
+        r.error = soa_capacity_error(p);
     }
     *res = r;
-    rs.ctl[kSelOk] = fits ? 1 : 0;
-    rs.ctl[kSelFirst] = 0;
-    rs.ctl[kSelCount] = count;
-    rs.ctl[kSelBasePl] = 0;
-    rs.ctl[kSelBaseUh] = 0;
-    rs.ctl[kSelTotPl] = tot_pl;
-    rs.ctl[kSelTotUh] = tot_uh;
-    rs.ctl[kSelExamined] = n;
+    soa_publish(rs.ctl, nullptr, p, count, tot_pl, tot_uh, n);
 }
 
 __global__ __launch_bounds__(256) void k_route_fields(iggy_unpacked_messages src, iggy_unpacked_messages o,
@@ -205,9 +175,9 @@ __global__ __launch_bounds__(256) void k_route_fields(iggy_unpacked_messages src
                                                       uint64_t *source_index, RouteScratch rs) {
     __shared__ uint32_t s_run[kRtParts];     // the next destination index of partition p
     __shared__ uint32_t s_cnt[4][kRtParts];  // this round's messages per wave and partition
-    if (!rs.ctl[kSelOk]) return;
+    if (!rs.ctl[kSoaOk]) return;
     const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const uint64_t n = rs.ctl[kSelExamined];
+    const uint64_t n = rs.ctl[kSoaAux];
     const uint64_t ntiles = (n + kRtTile - 1) / kRtTile;
     for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
         if (has_out && tid < partitions) s_run[tid] = rs.hist[t * partitions + tid];
@@ -232,18 +202,9 @@ __global__ __launch_bounds__(256) void k_route_fields(iggy_unpacked_messages src
             if (live) {
                 uint64_t d = (uint64_t)s_run[p] + rank;  // < count: the scan's verdict covers it
                 for (uint32_t w = 0; w < wave; ++w) d += s_cnt[w][p];
-                const uint32_t pl = sel_len(src.payload_lengths, src.payload_starts, i);
-                const uint32_t uh = sel_len(src.user_headers_lengths, src.user_headers_starts, i);
-                if (o.ids) {
-                    o.ids[2 * d] = src.ids[2 * i];
-                    o.ids[2 * d + 1] = src.ids[2 * i + 1];
-                }
-                if (o.checksums) o.checksums[d] = src.checksums[i];
-                if (o.offsets) o.offsets[d] = src.offsets[i];
-                if (o.timestamps) o.timestamps[d] = src.timestamps[i];
-                if (o.origin_timestamps) o.origin_timestamps[d] = src.origin_timestamps[i];
-                if (o.payload_lengths) o.payload_lengths[d] = pl;
-                if (o.user_headers_lengths) o.user_headers_lengths[d] = uh;
+                const uint32_t pl = soa_len(src.payload_lengths, src.payload_starts, i);
+                const uint32_t uh = soa_len(src.user_headers_lengths, src.user_headers_starts, i);
+                soa_scatter_fixed(src, i, o, d, pl, uh);
                 rs.dlens[d] = make_uint2(pl, uh);
                 rs.sidx[d] = i;
                 if (source_index) source_index[d] = i;
@@ -259,39 +220,9 @@ __global__ __launch_bounds__(256) void k_route_fields(iggy_unpacked_messages src
 }
 
 __global__ __launch_bounds__(256) void k_route_dscan(RouteScratch rs) {
-    __shared__ uint64_t s_pl[256], s_uh[256];
-    __shared__ uint64_t carry_pl, carry_uh;
-    if (!rs.ctl[kSelOk]) return;
-    const uint32_t tid = threadIdx.x;
-    const uint64_t ndt = (rs.ctl[kSelCount] + kRtDTile - 1) / kRtDTile;
-    if (tid == 0) { carry_pl = 0; carry_uh = 0; }
-    __syncthreads();
-    for (uint64_t t0 = 0; t0 < ndt; t0 += 256) {
-        const uint64_t t = t0 + tid;
-        const uint64_t vpl = t < ndt ? rs.dtile_pl[t] : 0;
-        const uint64_t vuh = t < ndt ? rs.dtile_uh[t] : 0;
-        s_pl[tid] = vpl;
-        s_uh[tid] = vuh;
-        __syncthreads();
-        for (uint32_t k = 1; k < 256; k <<= 1) {  // inclusive scan (Hillis-Steele in LDS, as k_sel_scan)
-            const uint64_t a = tid >= k ? s_pl[tid - k] : 0;
-            const uint64_t b = tid >= k ? s_uh[tid - k] : 0;
-            __syncthreads();
-            s_pl[tid] += a;
-            s_uh[tid] += b;
-            __syncthreads();
-        }
-        if (t < ndt) {
-            rs.dtile_pl[t] = carry_pl + s_pl[tid] - vpl;
-            rs.dtile_uh[t] = carry_uh + s_uh[tid] - vuh;
-        }
-        __syncthreads();
-        if (tid == 0) {
-            carry_pl += s_pl[255];
-            carry_uh += s_uh[255];
-        }
-        __syncthreads();
-    }
+    if (!rs.ctl[kSoaOk]) return;
+    uint64_t *const tiles[2] = {rs.dtile_pl, rs.dtile_uh};
+    soa_tile_offsets<false>(threadIdx.x, (rs.ctl[kSoaCount] + kRtDTile - 1) / kRtDTile, tiles, nullptr);
 }
 
 __global__ __launch_bounds__(256) void k_route_starts(iggy_unpacked_messages o, uint32_t partitions,
@@ -299,9 +230,9 @@ __global__ __launch_bounds__(256) void k_route_starts(iggy_unpacked_messages o, 
                                                       uint64_t *puh_first, RouteScratch rs) {
     __shared__ uint64_t s_pl[256], s_uh[256];
     __shared__ uint64_t s_first[kRtParts + 1];
-    if (!rs.ctl[kSelOk]) return;
+    if (!rs.ctl[kSoaOk]) return;
     const uint32_t tid = threadIdx.x;
-    const uint64_t count = rs.ctl[kSelCount];
+    const uint64_t count = rs.ctl[kSoaCount];
     const uint64_t ndt = (count + kRtDTile - 1) / kRtDTile;
     const bool tables = ppl_first || puh_first;
     if (tables)
@@ -319,14 +250,7 @@ __global__ __launch_bounds__(256) void k_route_starts(iggy_unpacked_messages o, 
         s_pl[tid] = a;
         s_uh[tid] = b;
         __syncthreads();
-        for (uint32_t k = 1; k < 256; k <<= 1) {
-            const uint64_t x = tid >= k ? s_pl[tid - k] : 0;
-            const uint64_t y = tid >= k ? s_uh[tid - k] : 0;
-            __syncthreads();
-            s_pl[tid] += x;
-            s_uh[tid] += y;
-            __syncthreads();
-        }
+        soa_scan(tid, s_pl, s_uh);
         uint64_t sp = rs.dtile_pl[t] + s_pl[tid] - a, su = rs.dtile_uh[t] + s_uh[tid] - b;
         for (uint32_t k = 0; k < kRtPer; ++k) {
             const uint64_t j = j0 + k;
@@ -352,7 +276,7 @@ __global__ __launch_bounds__(256) void k_route_starts(iggy_unpacked_messages o, 
         __syncthreads();
     }
     if (blockIdx.x == 0) {  // the end entries, and the partitions that start there (empty ones at the end)
-        const uint64_t tot_pl = rs.ctl[kSelTotPl], tot_uh = rs.ctl[kSelTotUh];
+        const uint64_t tot_pl = rs.ctl[kSoaTotPl], tot_uh = rs.ctl[kSoaTotUh];
         if (tid == 0) {
             if (o.payload_starts) o.payload_starts[count] = tot_pl;
             if (o.user_headers_starts) o.user_headers_starts[count] = tot_uh;
